@@ -25,7 +25,15 @@ upper-triangle uint8 round slabs all-gathered in place over RCCL/xGMI on a secon
 while the next round is computed, every GPU unpacking / mirroring them into the whole K),
 and the weak-scaled build (N = 100000 sqrt(G), every GPU 1e10 pairs) as `weak_scaled`.
 
-Also reported: the mismatch (k=9, m=1) Gram at N=20000 (BASELINE configs[2], float64
+A plain run (`bench.py --gpus G --steps N --warmup W`) is the headline alone: set-up, W
+warm-up builds, the N timed builds, the JSON line (`ms_per_step`: one timed build).  The
+other share shape, `shares_measured`, `assembled`, `weak_scaled`, the per-stage pass, the
+spot checks and everything in the next paragraph run under `--full`.  `--dump-outputs DIR`
+writes a fixed, seeded sample of whole rows of the K the last timed build left (rank 0's
+share) as DIR/K_rows.npy (float32, exact for these counts) with their row numbers in
+DIR/K_row_index.npy; the input is seeded, so two builds of the library can be compared.
+
+With --full also reported: the mismatch (k=9, m=1) Gram at N=20000 (BASELINE configs[2], float64
 normalised), per-stage device times from HIP events, the HBM roofline of the dominant
 kernel, the oracle timed on the host cores (cpu_baseline), and (N=1) BASELINE configs[1]
 (N=20000 spectrum) and [4], the drop-in host path, run.py's nine kernels at N=9000 and the downstream
@@ -193,12 +201,37 @@ def stage_means(ctx):
     return out
 
 
+SAMPLE_BYTES = 48 << 20  # --dump-outputs: at most this much of K is copied back and written
+SAMPLE_SEED = 20240
+
+
+def sample_rows(ctx, d_out, nrows, width, out_dtype):
+    """A fixed, seeded sample of whole rows of the row-major nrows x width device matrix at
+    d_out (the first and the last row always among them), at most SAMPLE_BYTES of float32 /
+    float64: (row numbers as float64, the rows -- integer counts as float32, exact below
+    2^24; float64 as it is)."""
+    dt = np.dtype(L.DTYPES[out_dtype])
+    fdt = np.float64 if dt == np.float64 else np.float32
+    k = int(max(1, min(nrows, SAMPLE_BYTES // (width * np.dtype(fdt).itemsize))))
+    rng = np.random.default_rng(SAMPLE_SEED)
+    inner = 1 + rng.permutation(max(0, nrows - 2))[:max(0, k - 2)]
+    idx = np.unique(np.r_[0, nrows - 1, inner])[:k].astype(np.int64)
+    out = np.empty((len(idx), width), dtype=fdt)
+    row = np.empty(width, dtype=dt)
+    for i, r in enumerate(idx):
+        ctx.d2h(row, ctypes.c_void_p(d_out.value + int(r) * width * dt.itemsize))
+        out[i] = row
+    return idx.astype(np.float64), out
+
+
 def run_build(ctx, dist, name, params, out_dtype, n, seed, steps, warmup, check_row,
-              gather=None):
+              gather=None, full=True, sample=False):
     """Timed full-K builds of one workload: kmg_gram_blocks over this rank's block-cyclic
     rows; gather (default: GATHER_MODE when G > 1) all-gathers them in place over RCCL,
     0 keeps every rank to its own rows (no data-path collective).  Returns timings, stages
-    and a spot check."""
+    and a spot check.  full=False: the warm-up and the timed steps only (no per-stage pass,
+    no spot check against the oracle, no fill rate).  sample: res["sample"] = sample_rows of
+    this rank's K as the last timed step left it."""
     codes, lens = E.synthetic(n, 101, seed=seed)
     ldc = codes.shape[1]
     esz = np.dtype(L.DTYPES[out_dtype]).itemsize
@@ -243,6 +276,12 @@ def run_build(ctx, dist, name, params, out_dtype, n, seed, steps, warmup, check_
             dist.barrier()
             wall = dist.max(time.perf_counter() - t0)
             kern = stage_means(ctx)
+            if sample and "sample" not in res:
+                res["sample"] = sample_rows(ctx, d_out, res["rows_this_rank"] if packed else n,
+                                            n, out_dtype)
+            if not full:
+                ctx.set_timing(False)
+                return wall / k, kern
             # per-stage breakdown (index build etc.) from a separate, untimed pass
             ctx.set_timing(True)
             ctx.timing_reset()
@@ -257,6 +296,8 @@ def run_build(ctx, dist, name, params, out_dtype, n, seed, steps, warmup, check_
         t, stages = timed(gather, steps)
         res.update({"ms_per_step": t * 1e3, "pairs_per_s": n * n / t, "stages_ms": stages,
                     "wire_bytes": ctx.blocks_wire(), "plan": ctx.last_plan()})
+        if not full:
+            return res
         if gather:
             tcf, scf = timed(0, steps)
             res["collective_free"] = {"ms_per_step": tcf * 1e3, "pairs_per_s": n * n / tcf,
@@ -567,9 +608,10 @@ def share_mode(n, world):
 
 
 def run_colshare(ctx, dist, name, params, out_dtype, n, seed, steps, warmup, oracle_row,
-                 world=None, rank=None):
+                 world=None, rank=None, full=True, sample=False):
     """Timed column-block shares (kmg_gram_device_cols): rank r computes K[:, C_r] of all n
     rows, C_r = rank_rows(n, G, r) -- by symmetry the row share K[C_r, :], column-major.
+    full / sample: as in run_build.
     world / rank given: that rank's share of a G-rank job timed on this one GPU (the
     collective-free build has no exchange, so its per-rank time is the job's).  Timed like
     run_build: HIP events around the Gram launch, barrier + synchronise on both sides, the
@@ -605,6 +647,13 @@ def run_colshare(ctx, dist, name, params, out_dtype, n, seed, steps, warmup, ora
         dist.barrier()
         t = dist.max(time.perf_counter() - t0) / steps
         kern = stage_means(ctx)
+        if sample:
+            res["sample"] = sample_rows(ctx, d_out, n, w, out_dtype)
+        if not full:
+            ctx.set_timing(False)
+            res.update({"ms_per_step": t * 1e3, "pairs_per_s": n * n / t, "stages_ms": kern,
+                        "plan": ctx.last_plan()})
+            return res
         ctx.set_timing(True)
         ctx.timing_reset()
         for _ in range(min(steps, 5)):
@@ -833,6 +882,9 @@ def host_path_config4(ctx, n=100000, slab_rows=2500, f64=True):
         rc = hip.hipHostMalloc(ctypes.byref(hp), ctypes.c_size_t(total), 0)
         out["pinned_alloc_s"] = time.perf_counter() - t0
         if rc != 0 or not hp.value:
+            # the runtime keeps the failure as this thread's last error until it is read: left
+            # there, the next kernel launch of the library would report it as its own
+            hip.hipGetLastError()
             hp = ctypes.c_void_p()
             out["error"] = f"hipHostMalloc({total}) = {rc}"
             return out
@@ -1268,9 +1320,21 @@ def main():
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--no-extra", action="store_true",
                     help="skip the config 4 / 5, host-path, run.py and downstream lines")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the CPU baselines, the per-stage pass, spot checks "
+                         "against the oracle, the fill rate, the G = 2 / 4 / 8 shares, the "
+                         "mismatch build, configs 2 / 4 / 5, the host path, run.py's kernels, the "
+                         "downstream solvers, the G > 1 assembled / weak-scaled builds and the "
+                         "projection (bench_details.json); the --no-* options trim these")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write a fixed, seeded sample of whole rows of "
+                         "the K the last timed step built (rank 0's share) to DIR/K_rows.npy "
+                         "(float32) and their row numbers to DIR/K_row_index.npy (float64)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     # `--gpus G` alone (no launcher environment): this process starts the G ranks itself,
     # before anything here touches the GPU, and relays rank 0's line
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -1309,6 +1373,10 @@ def main():
                   file=json_out, flush=True)
         dist.close()
         return
+    full = args.full
+    if not full:
+        # a plain run is the headline alone: set-up, warm-up, the timed steps, the line
+        args.no_cpu = args.no_mismatch = args.no_weak = args.no_extra = True
     n1 = args.n
     sp_seed = 4 if n1 == 100000 else 2
     # the CPU baseline runs FIRST, before this process makes any HIP call: its workers are
@@ -1323,7 +1391,7 @@ def main():
     ctx = L.Context(int(dev) if dev is not None else dist.local)
     # KMG_BENCH_NO_RCCL=1: the collective-free lines only (a rehearsal of the G > 1 headline
     # with several ranks on one GPU, where RCCL refuses duplicate devices)
-    rccl = dist.world > 1 and os.environ.get("KMG_BENCH_NO_RCCL") != "1"
+    rccl = full and dist.world > 1 and os.environ.get("KMG_BENCH_NO_RCCL") != "1"
     rccl_error = None
     if rccl:
         # the communicator is the only RCCL step every G > 1 line needs; if it cannot be
@@ -1349,17 +1417,29 @@ def main():
     # and the weak-scaled build (N = n1 sqrt(G)) `weak_scaled`
     n = n1
     mode = share_mode(n, dist.world)
-    sp_rows = run_build(ctx, dist, "spectrum_k8", P.make(L.KMG_SPECTRUM, k=8), L.KMG_I32, n,
-                        sp_seed, args.steps, args.warmup, check_spectrum, gather=0)
-    sp_rows["share"] = "rows"
-    sp_rows["rows_per_rank"] = dist.gather(sp_rows["rows_this_rank"])
-    sp_cols = None
-    if dist.world > 1:
+    dump = bool(args.dump_outputs)
+    sp_rows = sp_cols = None
+    if full or mode == "rows":
+        sp_rows = run_build(ctx, dist, "spectrum_k8", P.make(L.KMG_SPECTRUM, k=8), L.KMG_I32, n,
+                            sp_seed, args.steps, args.warmup, check_spectrum, gather=0,
+                            full=full, sample=dump and mode == "rows")
+        sp_rows["share"] = "rows"
+        sp_rows["rows_per_rank"] = dist.gather(sp_rows["rows_this_rank"])
+    if dist.world > 1 and (full or mode == "cols"):
         sp_cols = run_colshare(ctx, dist, "spectrum_k8", P.make(L.KMG_SPECTRUM, k=8), L.KMG_I32,
-                               n, sp_seed, args.steps, args.warmup, spectrum_row)
+                               n, sp_seed, args.steps, args.warmup, spectrum_row,
+                               full=full, sample=dump and mode == "cols")
         sp_cols["cols_per_rank"] = dist.gather(sp_cols["cols_this_rank"])
     sp, sp_other = (sp_cols, sp_rows) if mode == "cols" else (sp_rows, sp_cols)
     sp["devices_per_rank"] = dist.gather(ctx.device)
+    if dump:
+        # what a caller of the timed path holds after its last step: this rank's K (rows
+        # K[R_g, :], or at G >= 4 the column block K[:, C_g]); rank 0 writes its sample
+        idx, rows = sp.pop("sample")
+        if dist.rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "K_rows.npy"), rows)
+            np.save(os.path.join(args.dump_outputs, "K_row_index.npy"), idx)
     shares = None
     if dist.world == 1 and not args.no_extra:
         shares = measured_shares(ctx, dist, n, sp_seed, max(10, args.steps), args.warmup,
@@ -1451,8 +1531,12 @@ def main():
                    "rccl": rccl, "rccl_error": rccl_error,
                    "parallelism": f"{'row' if mode == 'rows' else 'column'}-blocks x{dist.world}",
                    "out_dtype": "int32", "full_k_build_ms": sp["ms_per_step"]},
-        "stages_ms": sp["stages_ms"], "roofline": roof, "spot_check": sp["spot_check"],
+        "stages_ms": sp["stages_ms"], "roofline": roof, "full": full,
     }
+    if full:
+        line["spot_check"] = sp["spot_check"]
+    if dump:
+        line["dump_outputs"] = {"dir": args.dump_outputs, "files": ["K_rows.npy", "K_row_index.npy"]}
     if shares:
         # the G-rank headline's per-rank share, timed here (collective-free: its time is the
         # job's); speedup = the one-GPU full build / the share
@@ -1534,18 +1618,20 @@ def main():
     # keeps compact forms and ends with the configs 2 / 5 and configs[2] (secondary) numbers,
     # so the driver's 2000-character stdout tail holds them.
     details = {"configs": extra, "secondary": line.get("secondary")}
-    if dist.world == 1:
+    if dist.world == 1 and full:
         details["projection"] = projection(sp, n, extra)
         line["projection_g8"] = _projection_summary(details["projection"])
     if extra:
         line["configs"] = _compact_configs(extra)
     if "secondary" in line:
         line["secondary"] = _compact_record(line.pop("secondary"))
-    line["details_file"] = "bench_details.json"
+    if full:
+        line["details_file"] = "bench_details.json"
     if dist.rank == 0:
         try:
-            with open(os.path.join(ROOT, "bench_details.json"), "w") as f:
-                json.dump(details, f, indent=1, default=str)
+            if full:
+                with open(os.path.join(ROOT, "bench_details.json"), "w") as f:
+                    json.dump(details, f, indent=1, default=str)
         except OSError as e:
             line["details_file"] = "unwritable: %r" % (e,)
         print(json.dumps(line), file=json_out, flush=True)

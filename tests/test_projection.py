@@ -94,3 +94,35 @@ def test_bench_headline_share_shapes():
     assert bench.sp_kernel_name({"chunk": 20000, "nchunks": 5}) == "kmg::gram_sp_kernel<true,1,true,1>"
     assert bench.sp_kernel_name({"chunk": 25000, "nchunks": 1}) == "kmg::gram_sp_kernel<true,1,false,1>"
     assert bench.sp_kernel_name({"chunk": 12504, "nchunks": 1}) == "kmg::gram_sp_kernel<true,1,false,2>"
+
+
+def test_bench_dump_sample_is_fixed_and_bounded(monkeypatch):
+    """bench.sample_rows (--dump-outputs): whole rows of the device matrix, the first and the
+    last among them, the same rows on every call, float32 for integer counts and float64 as
+    it is, and never more than SAMPLE_BYTES."""
+    import ctypes
+    import numpy as np
+    sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
+    import bench
+
+    class HostCtx:  # d2h from a "device" pointer that is host memory
+        def d2h(self, dst, src):
+            ctypes.memmove(dst.ctypes.data, src.value, dst.nbytes)
+
+    for dt, code, fdt in ((np.int32, bench.L.KMG_I32, np.float32),
+                          (np.float64, bench.L.KMG_F64, np.float64)):
+        M = np.arange(37 * 11, dtype=dt).reshape(37, 11)
+        monkeypatch.setattr(bench, "SAMPLE_BYTES", 5 * 11 * np.dtype(fdt).itemsize)
+        idx, rows = bench.sample_rows(HostCtx(), ctypes.c_void_p(M.ctypes.data), 37, 11, code)
+        idx2, rows2 = bench.sample_rows(HostCtx(), ctypes.c_void_p(M.ctypes.data), 37, 11, code)
+        assert idx.dtype == np.float64 and rows.dtype == fdt
+        assert len(idx) == 5 and idx[0] == 0 and idx[-1] == 36 and len(set(idx)) == 5
+        assert rows.nbytes <= bench.SAMPLE_BYTES
+        assert np.array_equal(idx, idx2) and np.array_equal(rows, rows2)
+        assert np.array_equal(rows, M[idx.astype(int)].astype(fdt))
+        monkeypatch.setattr(bench, "SAMPLE_BYTES", 1 << 20)  # room for every row
+        idx, rows = bench.sample_rows(HostCtx(), ctypes.c_void_p(M.ctypes.data), 37, 11, code)
+        assert np.array_equal(idx, np.arange(37)) and np.array_equal(rows, M.astype(fdt))
+        for nrows in (1, 2):  # no interior rows to draw from
+            idx, rows = bench.sample_rows(HostCtx(), ctypes.c_void_p(M.ctypes.data), nrows, 11, code)
+            assert np.array_equal(idx, np.arange(nrows)) and np.array_equal(rows, M[:nrows].astype(fdt))

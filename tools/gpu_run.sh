@@ -6,7 +6,7 @@
 #   tests[=EXPR]            GPU test suite (tools/gpu_tests.sh; EXPR: pytest -k expression),
 #                           log gpurun_out/<tag>/pytest.txt
 #   smoke                   __graft_entry__.smoke()
-#   bench[:ARGS]            python bench.py ARGS (colon-separated, e.g. bench:--steps:10)
+#   bench[:ARGS]            python bench.py ARGS (colon-separated, e.g. bench:--full:--steps:10)
 #   benchprof[:ARGS]        the same under rocprofv3 --kernel-trace --stats
 #   prof:WL[,WL...]         rocprofv3 kernel trace + PMC passes (profiles/run_profiles_r02.sh)
 #   ab:<cfg json>@@<sets json>   interleaved A/B of KMG_* settings (tools/ab_env.py)
