@@ -142,6 +142,39 @@ int kmg_gram_device_cols(kmg_ctx *ctx, const kmg_params *p, const uint8_t *d_cod
                          int64_t col1, int32_t out_dtype, void *d_out, int64_t ld_out);
 
 /*
+ * Scoring new sequences against a fitted model without a Gram block: the prediction step
+ * f(q) = sum_t coef[t] K(q, x_t) + bias of KRR.predict (KRR.py:43-56) and C_SVM.predict
+ * (SVM.py:99-111), which the reference serves by slicing a K that already holds the new rows.
+ * Spectrum and mismatch are inner products of explicit feature maps over the 4^k k-mers, so
+ * the model is one table U of 4^k doubles and f(q) = sum over the windows a of q of U[q_a]
+ * (/ sqrt(K_qq) under normalize_K) + bias.  A scorer owns U and its parameters only; the
+ * index, records and DP tables of its construction stay in the context workspace.
+ *   Supported: KMG_SPECTRUM 1 <= k <= 12; KMG_MISMATCH 1 <= k <= 12, 0 <= m <= 2; normalize
+ *   0 or 1 (coef[t] / sqrt(K_tt) folded into U; skipped when K_00 == 1 on the training rows,
+ *   as normalize_K skips it).  Anything else (other families, k > 12, m > 2, la_mode != 0)
+ *   is KMG_EUNSUPPORTED before any allocation.  Mismatch rows shorter than the window are
+ *   KMG_EINVAL on either side, as in kmg_gram.
+ *   A query with no valid window scores bias (NaN under normalisation: 0 / 0, as the Gram
+ *   epilogue gives).  Two scorers built from the same inputs hold byte-identical tables.
+ */
+typedef struct kmg_scorer kmg_scorer;
+/* KRR.py:43-56 / SVM.py:99-111: the support vectors (codes, lens: n host rows) and their
+ * coefficients coef[n] become the table.  Synchronous. */
+int kmg_scorer_create(kmg_ctx *ctx, const kmg_params *p, const uint8_t *codes, const int32_t *lens,
+                      int64_t n, int64_t ldc, const double *coef, kmg_scorer **out);
+/* KRR.py:43-56 / SVM.py:99-111: out[q] = f(q) for nq host rows.  Synchronous. */
+int kmg_scorer_score(kmg_ctx *ctx, const kmg_scorer *s, const uint8_t *codes, const int32_t *lens,
+                     int64_t nq, int64_t ldc, double bias, double *out);
+/* KRR.py:43-56 / SVM.py:99-111 on device pointers: runs on the context stream and returns
+ * without synchronising. */
+int kmg_scorer_score_device(kmg_ctx *ctx, const kmg_scorer *s, const uint8_t *d_codes,
+                            const int32_t *d_lens, int64_t nq, int64_t ldc, double bias,
+                            double *d_out);
+/* Frees the table of a scorer of KRR.py:43-56 / SVM.py:99-111 (after the stream drains).
+ * ctx may be NULL when the context was destroyed first; the table is freed all the same. */
+int kmg_scorer_destroy(kmg_ctx *ctx, kmg_scorer *s);
+
+/*
  * The full K of all n rows into HOST memory h_out (row stride ld_host elements; e.g. a
  * memory-mapped .npy), built on the device in slabs of slab_rows rows: the posting index /
  * features / diagonal are built once for all slabs, and slab t's device-to-host copy (a
@@ -277,10 +310,11 @@ int kmg_svm_fit_device(kmg_ctx *ctx, const double *d_K, int64_t ld, int64_t n,
  * one-GPU rehearsal of the multi-rank assembly; no RCCL).  gather = 4: like 0 (no data-path
  * collective) with this rank's blocks packed: row t*block + y of d_out holds row
  * t*R + rank*block + y of K (d_out needs ceil(n / R) * block rows: a rank's share of a K
- * that no single GPU could hold).  gather = 5 (column blocks, mismatch (k, 1) with 4 <= k <= 12
- * only, KMG_EUNSUPPORTED otherwise): one round, nranks * block >= n; rank r computes the column
- * block K[:, C_r], C_r = [r*block, min(n, (r+1)*block)), with the neighbourhood lists built over
- * its own |C_r| sequences (kmg_gram_device_cols), transposes it into K's rows C_r (K is
+ * that no single GPU could hold).  gather = 5 (column blocks: mismatch (k, 1) with 4 <= k <= 12,
+ * or the spectrum posting-list path, 6 <= k <= 12; KMG_EUNSUPPORTED otherwise): one round,
+ * nranks * block >= n; rank r computes the column block K[:, C_r], C_r = [r*block,
+ * min(n, (r+1)*block)), with the neighbourhood lists / posting index built over its own |C_r|
+ * sequences (kmg_gram_device_cols), transposes it into K's rows C_r (K is
  * symmetric) and the slabs are all-gathered in place over RCCL; d_out holds nranks * block rows.
  * gather = 6: the gather = 5 layout with every rank's block computed on this GPU (no RCCL).
  * gather = 1, 2 or 5 with nranks > 1 needs kmg_comm_init with the same nranks / rank.  Replaces the whole-matrix pair loops of get_spectrum_K /
@@ -313,6 +347,7 @@ int kmg_stream(kmg_ctx *ctx, void **hip_stream);
  * Stage names: "count", "scan", "place", "fine", "diag", "gram", "extract", "features",
  * "pack" (2-bit packing of the input), "slots" (mismatch slot / pair tables, neighbourhood
  * lists), "lists" (neighbourhood-list sizes and starts), "combine",
+ * "vtab" / "butterfly" / "score" (kmg_scorer_*: weight table, Hamming DP, query scoring),
  * "solve", "memset", "gather" (the RCCL all-gathers of kmg_gram_blocks, timed on their own
  * stream), "unpack" (round-slab assembly), "mirror" (lower block triangle of a full square
  * mismatch K built by its upper block triangle).

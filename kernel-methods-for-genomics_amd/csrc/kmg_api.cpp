@@ -93,12 +93,13 @@ struct DevBuf {
 const char *kStageNames[] = {"count",   "scan",     "place", "fine",    "diag",
                              "gram",    "extract",  "pack",  "features", "combine",
                              "solve",   "slots",    "memset", "gather", "unpack",
-                             "mirror",  "lists",    "nbfill"};
-constexpr int kNumStages = 18;
+                             "mirror",  "lists",    "nbfill", "vtab",   "butterfly",
+                             "score"};
+constexpr int kNumStages = 21;
 enum {
   ST_COUNT, ST_SCAN, ST_PLACE, ST_FINE, ST_DIAG, ST_GRAM, ST_EXTRACT, ST_PACK, ST_FEATURES,
   ST_COMBINE, ST_SOLVE, ST_SLOTS, ST_MEMSET, ST_GATHER, ST_UNPACK, ST_MIRROR, ST_LISTS,
-  ST_NBFILL
+  ST_NBFILL, ST_VTAB, ST_BUTTERFLY, ST_SCORE
 };
 
 // Tuning knobs: read from the environment once per context (kmg_create) and again only on
@@ -241,6 +242,7 @@ struct kmg_ctx {
   DevBuf nb_seg, nb_use, nb_lines;  // neighbourhood lists: segment ends, pieces in use, lists
   DevBuf chk;                       // KMG_CHECK: validation flag + first offending list
   DevBuf cb_scratch;                // column-block assembly: one rank's K[:, C_q] (n x block)
+  DevBuf sc_fix, sc_tab;            // kmg_scorer_create: fixed-point weights, the DP tables
   Tuning tune;
   DevBuf cmb_k, cmb_ptrs, cmb_vec, cmb_out, cmb_tmp;  // combination consumers (host path)
   DevBuf sv_mat, sv_vec, sv_info;  // dense learners: factorised system, vectors, info/ipiv
@@ -1559,7 +1561,8 @@ int kmg_destroy(kmg_ctx *c) {
                     &c->cmb_out, &c->cmb_tmp, &c->sv_mat, &c->sv_vec, &c->sv_info, &c->sv_inv, &c->sv_panel,
                     &c->tri_stage, &c->tri_scratch, &c->dense_tiles, &c->ovf, &c->slabs,
                     &c->gcoef, &c->feat32, &c->k32, &c->ft_cols,
-                    &c->nb_seg, &c->nb_use, &c->nb_lines, &c->chk, &c->cb_scratch};
+                    &c->nb_seg, &c->nb_use, &c->nb_lines, &c->chk, &c->cb_scratch,
+                    &c->sc_fix, &c->sc_tab};
   for (DevBuf *b : bufs) b->release();
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
   if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
@@ -1734,6 +1737,275 @@ int kmg_gram_device_cols(kmg_ctx *c, const kmg_params *p, const uint8_t *d_codes
   KMG_HIP(hipSetDevice(c->device));
   return gram_device(c, p, d_codes, d_lens, (int)ldc, n, ldc, {RowRange{0, n, d_out}},
                      out_dtype, ld_out, nullptr, col0, col1 - col0);
+}
+
+// ----------------------------------------------------------------- scorer (kmg_score.hip)
+// A fitted model as one table U over the 4^k k-mers: f(q) = sum_a U[q_a] / sqrt(K_qq) + b.
+struct kmg_scorer {
+  int kind = 0, k = 0, m = 0, window = 0;
+  int device = 0;          // HIP device of the context that built it
+  bool norm = false;      // normalize_K applied (requested and K_00 != 1 on the training rows)
+  int maxd = 0;            // largest Hamming distance with a non-zero weight
+  int64_t w[33] = {};      // mismatch_weights (spectrum: 1, 0, ...)
+  DevBuf U, wtab;          // 4^k doubles; the weights on the device (the queries' diagonal)
+};
+
+static int scorer_check_params(const kmg_params *p) {
+  if (!p) return fail(KMG_EINVAL, "params is NULL");
+  if (p->kind != KMG_SPECTRUM && p->kind != KMG_MISMATCH)
+    return fail(KMG_EUNSUPPORTED, "scorer: spectrum or mismatch only (kind %d)", p->kind);
+  if (p->k < 1 || p->k > 12) return fail(KMG_EUNSUPPORTED, "scorer: 1 <= k <= 12 (k = %d)", p->k);
+  if (p->kind == KMG_MISMATCH && (p->m < 0 || p->m > 2))
+    return fail(KMG_EUNSUPPORTED, "scorer: mismatch 0 <= m <= 2 (m = %d)", p->m);
+  if (p->la_mode != 0) return fail(KMG_EUNSUPPORTED, "scorer: la_mode %d", p->la_mode);
+  if (p->normalize != 0 && p->normalize != 1) return fail(KMG_EINVAL, "normalize must be 0 or 1");
+  return KMG_OK;
+}
+
+// host rows: lens inside [0, ldc]; mismatch rows no shorter than the window (the Gram path's rule)
+static int scorer_check_rows(int kind, int window, const uint8_t *codes, const int32_t *lens,
+                             int64_t n, int64_t ldc, int *maxlen) {
+  if (n < 0 || ldc <= 0) return fail(KMG_EINVAL, "bad shape");
+  if (n > 0 && (!codes || !lens)) return fail(KMG_EINVAL, "NULL buffer");
+  *maxlen = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    if (lens[i] < 0 || lens[i] > ldc) return fail(KMG_EINVAL, "lens[%lld] outside [0,ldc]", (long long)i);
+    if (kind == KMG_MISMATCH && lens[i] < window)
+      return fail(KMG_EINVAL, "mismatch kernel needs sequences of length >= %d", window);
+    *maxlen = std::max(*maxlen, (int)lens[i]);
+  }
+  return KMG_OK;
+}
+
+int kmg_scorer_create(kmg_ctx *c, const kmg_params *p, const uint8_t *codes, const int32_t *lens,
+                      int64_t n, int64_t ldc, const double *coef, kmg_scorer **out) {
+  if (!c) return fail(KMG_EINVAL, "ctx is NULL");
+  if (!out) return fail(KMG_EINVAL, "out is NULL");
+  *out = nullptr;
+  std::lock_guard<std::mutex> lk(c->mu);
+  KMG_TRY(scorer_check_params(p));
+  const bool mm = p->kind == KMG_MISMATCH;
+  const int k = p->k, W = mm ? (p->window > 0 ? p->window : 101) : 0;
+  if (n < 1 || !coef) return fail(KMG_EINVAL, "scorer: no training rows / coef is NULL");
+  int maxlen = 0;
+  KMG_TRY(scorer_check_rows(p->kind, W, codes, lens, n, ldc, &maxlen));
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(coef[i])) return fail(KMG_EINVAL, "coef[%lld] is not finite", (long long)i);
+  KMG_HIP(hipSetDevice(c->device));
+  c->last_call_first = (int)c->ev_log.size();
+
+  std::unique_ptr<kmg_scorer> s(new kmg_scorer());
+  s->kind = p->kind;
+  s->device = c->device;
+  s->k = k;
+  s->m = mm ? p->m : 0;
+  s->window = W;
+  if (mm) {
+    mismatch_weights(k, p->m, s->w);
+  } else {
+    s->w[0] = 1;
+  }
+  for (int d = 0; d <= 32; ++d)
+    if (s->w[d] != 0) s->maxd = d;
+  struct Release {  // a failed create leaves nothing behind
+    kmg_scorer *s;
+    ~Release() {
+      if (s) {
+        s->U.release();
+        s->wtab.release();
+      }
+    }
+  } guard{s.get()};
+
+  // exact-key posting index of the training rows (the records are packed on the way)
+  IndexGeom g{};
+  g.k = k;
+  g.n = n;
+  g.window = W;
+  const int L = mm ? W : maxlen;
+  g.pmax = L - k + 1 > 0 ? L - k + 1 : 1;
+  if (g.pmax > 4095) return fail(KMG_EUNSUPPORTED, "more than 4095 k-mers per sequence");
+  g.copies = 1;
+  g.nkeys = (uint32_t)pow4(k);
+  choose_chunks(g, 32768);
+  const int cw = packed_cw(ldc), mw = packed_mw(ldc);
+  KMG_TRY(c->h_codes.ensure((size_t)n * ldc));
+  KMG_TRY(c->h_lens.ensure(sizeof(int32_t) * (size_t)n));
+  KMG_TRY(c->packed.ensure(sizeof(uint32_t) * (size_t)n * (cw + mw)));
+  KMG_TRY(s->U.ensure(sizeof(double) * (size_t)pow4(k)));
+  KMG_TRY(s->wtab.ensure(sizeof(int64_t) * 33));
+  KMG_HIP(hipMemcpyAsync(c->h_codes.p, codes, (size_t)n * ldc, hipMemcpyHostToDevice, c->stream));
+  KMG_HIP(hipMemcpyAsync(c->h_lens.p, lens, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
+  KMG_HIP(hipMemcpyAsync(s->wtab.p, s->w, sizeof(s->w), hipMemcpyHostToDevice, c->stream));
+  const Packed pkd{c->packed.as<uint32_t>(), (int64_t)(cw + mw), cw};
+  KMG_TRY(build_index(c, g, pkd, c->h_codes.as<uint8_t>(), c->h_lens.as<int32_t>(), ldc));
+
+  // beta_t = coef_t, or coef_t / sqrt(K_tt) under normalize_K (skipped, as the Gram epilogue
+  // skips it, when K_00 == 1)
+  std::vector<double> beta(coef, coef + n);
+  if (p->normalize) {
+    KMG_TRY(c->diagv.ensure(sizeof(double) * (size_t)n));
+    KMG_TRY(c->dsq.ensure(sizeof(double) * (size_t)n));
+    {
+      StageTimer t(c, ST_DIAG);
+      KMG_HIP(launch_diag_hamming(g, pkd, s->wtab.as<int64_t>(), s->maxd, c->diagv.as<double>(),
+                                  c->dsq.as<double>(), c->stream));
+    }
+    std::vector<double> dsq((size_t)n);
+    double d0 = 0.0;
+    KMG_HIP(hipMemcpyAsync(dsq.data(), c->dsq.p, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    KMG_HIP(hipMemcpyAsync(&d0, c->diagv.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    KMG_HIP(hipStreamSynchronize(c->stream));
+    s->norm = d0 != 1.0;
+    if (s->norm)
+      for (int64_t i = 0; i < n; ++i) {
+        if (beta[i] == 0.0) continue;
+        if (!(dsq[i] > 0.0))
+          return fail(KMG_EINVAL, "scorer: training row %lld has no valid window, its normalised "
+                      "kernel row is 0/0", (long long)i);
+        beta[i] /= dsq[i];
+      }
+  }
+  // 128-bit fixed point, 90 fraction bits below 2^E > max |beta|: list sums stay below 2^127
+  // (fewer than 2^32 occurrences, build_index) and are exact in any order
+  double bmax = 0.0;
+  for (double b : beta) bmax = std::max(bmax, std::fabs(b));
+  int E = 0;
+  if (bmax > 0.0) (void)std::frexp(bmax, &E);
+  std::vector<uint64_t> fix((size_t)2 * n);
+  for (int64_t i = 0; i < n; ++i) {
+    // the magnitude first: hi = floor(|x| 2^-64) < 2^26 and lo = |x| - hi 2^64 < 2^64 are
+    // exact for a non-negative double (no double ever holds a rounded 64-bit-wide value);
+    // then the two's complement of the 128-bit integer for a negative beta
+    const double ax = std::ldexp(std::fabs(beta[i]), 90 - E);
+    const double hid = std::floor(std::ldexp(ax, -64));
+    uint64_t lo = (uint64_t)(ax - std::ldexp(hid, 64)), hi = (uint64_t)hid;
+    if (beta[i] < 0.0) {
+      lo = ~lo + 1;
+      hi = ~hi + (lo == 0 ? 1 : 0);
+    }
+    fix[2 * i] = lo;
+    fix[2 * i + 1] = hi;
+  }
+  KMG_TRY(c->sc_fix.ensure(sizeof(uint64_t) * fix.size()));
+  KMG_HIP(hipMemcpyAsync(c->sc_fix.p, fix.data(), sizeof(uint64_t) * fix.size(),
+                         hipMemcpyHostToDevice, c->stream));
+  const int nt = s->maxd + 1;  // DP tables T_0 .. T_min(2m, k)
+  const bool butterfly = mm && nt > 1;
+  double *V = s->U.as<double>();
+  if (mm) {  // (m = 0: U = w[0] V, one pass of the butterfly's last stage)
+    KMG_TRY(c->sc_tab.ensure(sizeof(double) * (size_t)nt * (size_t)pow4(k)));
+    V = c->sc_tab.as<double>();
+  }
+  {
+    StageTimer t(c, ST_VTAB);
+    KMG_HIP(launch_score_vtab(g, c->off.as<uint32_t>(), c->ent.as<uint16_t>(),
+                              c->sc_fix.as<uint64_t>(), E - 90, V, c->stream));
+  }
+  if (mm) {
+    int hb = 16;
+    const int t = score_tile_digits(nt, (size_t)c->lds_max, &hb);
+    double wd[5] = {0, 0, 0, 0, 0};
+    for (int h = 0; h < nt; ++h) wd[h] = (double)s->w[h];
+    StageTimer tm(c, ST_BUTTERFLY);
+    for (int lo = 0; lo < k; lo += t) {
+      const int tg = std::min(t, k - lo);
+      const bool last = !butterfly || lo + tg >= k;
+      KMG_HIP(launch_score_butterfly(V, k, nt, lo, tg, hb, lo == 0, last, wd, s->U.as<double>(),
+                                     c->stream));
+      if (last) break;
+    }
+  }
+  KMG_HIP(hipStreamSynchronize(c->stream));  // pageable sources; U is complete on return
+  guard.s = nullptr;
+  *out = s.release();
+  return KMG_OK;
+}
+
+// queries on the device -> d_out on the context stream (no lock, no synchronise)
+static int scorer_score_device(kmg_ctx *c, const kmg_scorer *s, const uint8_t *d_codes,
+                               const int32_t *d_lens, int64_t nq, int64_t ldc, double bias,
+                               double *d_out) {
+  c->last_call_first = (int)c->ev_log.size();
+  if (nq == 0) return KMG_OK;
+  const bool mm = s->kind == KMG_MISMATCH;
+  if (mm && ldc < s->window)
+    return fail(KMG_EINVAL, "mismatch: code rows (%lld) shorter than the window %d", (long long)ldc,
+                s->window);
+  const int cw = packed_cw(ldc), mw = packed_mw(ldc);
+  if ((int64_t)(cw + mw) > 1024) return fail(KMG_EUNSUPPORTED, "sequences longer than 8192");
+  const int64_t L = mm ? s->window : ldc;
+  const int P = (int)std::max<int64_t>(1, L - s->k + 1);
+  KMG_TRY(c->packed.ensure(sizeof(uint32_t) * (size_t)nq * (cw + mw)));
+  const Packed pk{c->packed.as<uint32_t>(), (int64_t)(cw + mw), cw};
+  {
+    StageTimer t(c, ST_PACK);
+    KMG_HIP(launch_pack(d_codes, d_lens, nq, ldc, s->window, c->packed.as<uint32_t>(), c->stream));
+  }
+  if (s->norm) {  // K_qq of every query
+    if (P > 4095) return fail(KMG_EUNSUPPORTED, "more than 4095 k-mers per sequence");
+    IndexGeom g{};
+    g.k = s->k;
+    g.n = nq;
+    g.window = s->window;
+    g.pmax = P;
+    KMG_TRY(c->diagv.ensure(sizeof(double) * (size_t)nq));
+    KMG_TRY(c->dsq.ensure(sizeof(double) * (size_t)nq));
+    StageTimer t(c, ST_DIAG);
+    KMG_HIP(launch_diag_hamming(g, pk, s->wtab.as<int64_t>(), s->maxd, c->diagv.as<double>(),
+                                c->dsq.as<double>(), c->stream));
+  }
+  StageTimer t(c, ST_SCORE);
+  KMG_HIP(launch_score(pk, nq, s->k, P, s->U.as<double>(), s->norm ? c->dsq.as<double>() : nullptr,
+                       bias, d_out, c->stream));
+  return KMG_OK;
+}
+
+int kmg_scorer_score_device(kmg_ctx *c, const kmg_scorer *s, const uint8_t *d_codes,
+                            const int32_t *d_lens, int64_t nq, int64_t ldc, double bias,
+                            double *d_out) {
+  if (!c || !s) return fail(KMG_EINVAL, "ctx / scorer is NULL");
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (nq < 0 || ldc <= 0) return fail(KMG_EINVAL, "bad shape");
+  if (nq > 0 && (!d_codes || !d_lens || !d_out)) return fail(KMG_EINVAL, "NULL buffer");
+  KMG_HIP(hipSetDevice(c->device));
+  return scorer_score_device(c, s, d_codes, d_lens, nq, ldc, bias, d_out);
+}
+
+int kmg_scorer_score(kmg_ctx *c, const kmg_scorer *s, const uint8_t *codes, const int32_t *lens,
+                     int64_t nq, int64_t ldc, double bias, double *out) {
+  if (!c || !s) return fail(KMG_EINVAL, "ctx / scorer is NULL");
+  std::lock_guard<std::mutex> lk(c->mu);
+  int maxlen = 0;
+  KMG_TRY(scorer_check_rows(s->kind, s->window, codes, lens, nq, ldc, &maxlen));
+  if (nq == 0) return KMG_OK;
+  if (!out) return fail(KMG_EINVAL, "NULL buffer");
+  KMG_HIP(hipSetDevice(c->device));
+  KMG_TRY(c->h_codes.ensure((size_t)nq * ldc));
+  KMG_TRY(c->h_lens.ensure(sizeof(int32_t) * (size_t)nq));
+  KMG_TRY(c->h_out.ensure(sizeof(double) * (size_t)nq));
+  KMG_HIP(hipMemcpyAsync(c->h_codes.p, codes, (size_t)nq * ldc, hipMemcpyHostToDevice, c->stream));
+  KMG_HIP(hipMemcpyAsync(c->h_lens.p, lens, sizeof(int32_t) * nq, hipMemcpyHostToDevice, c->stream));
+  KMG_TRY(scorer_score_device(c, s, c->h_codes.as<uint8_t>(), c->h_lens.as<int32_t>(), nq, ldc,
+                              bias, c->h_out.as<double>()));
+  KMG_HIP(hipMemcpyAsync(out, c->h_out.p, sizeof(double) * nq, hipMemcpyDeviceToHost, c->stream));
+  KMG_HIP(hipStreamSynchronize(c->stream));
+  return KMG_OK;
+}
+
+int kmg_scorer_destroy(kmg_ctx *c, kmg_scorer *s) {
+  if (!s) return KMG_OK;
+  // ctx may be NULL (a scorer that outlived its context): the table is still freed, on the
+  // scorer's own device; hipFree waits for the device's outstanding work itself
+  (void)hipSetDevice(s->device);
+  if (c) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    (void)hipStreamSynchronize(c->stream);
+  }
+  s->U.release();
+  s->wtab.release();
+  delete s;
+  return KMG_OK;
 }
 
 int kmg_gram_to_host(kmg_ctx *c, const kmg_params *p, const uint8_t *d_codes,

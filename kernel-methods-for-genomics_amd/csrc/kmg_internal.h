@@ -277,6 +277,23 @@ hipError_t launch_gram_hamming(const IndexGeom &g, const uint32_t *kmers, int64_
 hipError_t launch_diag_hamming(const IndexGeom &g, const Packed &pk, const int64_t *wtab,
                                int max_dist, double *diagv, double *dsq, hipStream_t s);
 
+// ---------------------------------------------------------------- scorer (kmg_score.hip)
+// V[key] = sum over the key's posting lists (exact index, copies = 1, every chunk) of the
+// 128-bit fixed-point weights fix[2 row], fix[2 row + 1] (low, high word), rounded once to
+// double and scaled by 2^scale_exp: exact integer sums, so any list order gives the same bits
+hipError_t launch_score_vtab(const IndexGeom &g, const uint32_t *off, const uint16_t *ent,
+                             const uint64_t *fix, int scale_exp, double *V, hipStream_t s);
+// digits a butterfly launch takes (tile of nt tables within lds_max); *hb = tile rows beside them
+int score_tile_digits(int nt, size_t lds_max, int *hb);
+// one launch of the Hamming DP over digits [lo, lo + tg) of the nt tables T (4^k doubles each,
+// T_0 = V): T_h += S_p T_{h-1} per digit, in place.  first: T_1.. are taken as zero;
+// last: U = sum_h w[h] T_h is written instead of the tables
+hipError_t launch_score_butterfly(double *T, int k, int nt, int lo, int tg, int hb, bool first,
+                                  bool last, const double *w, double *U, hipStream_t s);
+// out[q] = sum_{a < P} U[window a of record q] (/ dsq[q] when dsq != nullptr) + bias
+hipError_t launch_score(const Packed &pk, int64_t nq, int k, int P, const double *U,
+                        const double *dsq, double bias, double *out, hipStream_t s);
+
 struct SeqSpec {
   const uint8_t *codes;
   const int32_t *lens;

@@ -37,6 +37,7 @@ EXPORTS = (
     "kmg_svm_fit_device", "kmg_rows_padded", "kmg_gram_blocks", "kmg_reload_tuning",
     "kmg_gram_to_host", "kmg_gram_blocks_wire", "kmg_last_plan", "kmg_features",
     "kmg_last_factorisation", "kmg_features_sym", "kmg_gram_device_cols",
+    "kmg_scorer_create", "kmg_scorer_score", "kmg_scorer_score_device", "kmg_scorer_destroy",
 )
 KMG_FEATURES_BCAST = 1
 KMG_FACTOR_CHOLESKY, KMG_FACTOR_LU_ASYMMETRIC, KMG_FACTOR_LU_INDEFINITE = 1, 2, 3
@@ -99,6 +100,11 @@ def load():
                              ctypes.c_int),
             "kmg_features_sym": ([P, ctypes.POINTER(KmgParams), P, P, I64, I64, P, I64, I32, P,
                                   I64], ctypes.c_int),
+            "kmg_scorer_create": ([P, ctypes.POINTER(KmgParams), P, P, I64, I64, P,
+                                   ctypes.POINTER(P)], ctypes.c_int),
+            "kmg_scorer_score": ([P, P, P, P, I64, I64, D, P], ctypes.c_int),
+            "kmg_scorer_score_device": ([P, P, P, P, I64, I64, D, P], ctypes.c_int),
+            "kmg_scorer_destroy": ([P, P], ctypes.c_int),
             "kmg_normalize": ([P, P, I64, I64, ctypes.POINTER(I32)], ctypes.c_int),
             "kmg_center": ([P, P, I64, P, I64, I64], ctypes.c_int),
             "kmg_dmalloc": ([P, ctypes.POINTER(P), SZ], ctypes.c_int),
@@ -172,6 +178,40 @@ def ptr(a):
     return ctypes.c_void_p(a.ctypes.data) if a is not None else None
 
 
+class Scorer:
+    """A fitted spectrum / mismatch model as one k-mer table on the device (kmg_scorer_*)."""
+
+    def __init__(self, ctx, handle):
+        self.ctx = ctx
+        self._h = handle
+
+    def score(self, codes, lens, bias=0.0):
+        """float64 [nq]: f(q) = sum_t coef[t] K(q, x_t) + bias for every row of codes."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        nq, ldc = codes.shape
+        out = np.empty(nq, dtype=np.float64)
+        check(self.ctx.lib.kmg_scorer_score(self.ctx.handle, self._h, ptr(codes), ptr(lens), nq,
+                                            ldc, float(bias), ptr(out)))
+        return out
+
+    def score_device(self, d_codes, d_lens, nq, ldc, bias, d_out):
+        """The same on device pointers, on the context stream, without synchronising."""
+        check(self.ctx.lib.kmg_scorer_score_device(self.ctx.handle, self._h, d_codes, d_lens, nq,
+                                                   ldc, float(bias), d_out))
+
+    def close(self):
+        if self._h:  # a closed context passes NULL: the table is freed all the same
+            self.ctx.lib.kmg_scorer_destroy(self.ctx.handle, self._h)
+        self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     """One libkmgram context (one HIP device, one stream, a device workspace)."""
 
@@ -231,6 +271,20 @@ class Context:
         check(self.lib.kmg_features_sym(self._h, ctypes.byref(params), ptr(codes), ptr(lens), n,
                                         ldc, ptr(cols), len(cols), int(flags), ptr(out), len(cols)))
         return out
+
+    def scorer(self, params, codes, lens, coef):
+        """Scorer of the model sum_t coef[t] K(., row t) over the rows of codes
+        (kmg_scorer_create): spectrum / mismatch, k <= 12."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        coef = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1)
+        n, ldc = codes.shape
+        if coef.shape[0] != n:
+            raise ValueError(f"coef has {coef.shape[0]} entries for {n} rows")
+        h = ctypes.c_void_p()
+        check(self.lib.kmg_scorer_create(self._h, ctypes.byref(params), ptr(codes), ptr(lens), n,
+                                         ldc, ptr(coef), ctypes.byref(h)))
+        return Scorer(self, h)
 
     def gram_device(self, params, d_codes, d_lens, n, ldc, row0, row1, out_dtype, d_out, ld):
         check(self.lib.kmg_gram_device(self._h, ctypes.byref(params), d_codes, d_lens, n, ldc,

@@ -178,6 +178,39 @@ class GramEngine:
             gappy_reference_errors(len(s), k, g)
         return self._run(P.make(L.KMG_GAPPY, k=k, g=g, window=101), seqs)
 
+    # ------------------------------------------------------------------ scoring
+    def scorer(self, method, seqs, coef):
+        """Scorer of f(q) = sum_t coef[t] K(q, seqs[t]) + bias for K = select_method(., method),
+        without building any K (kmg_scorer_create).  ``method`` follows select_method's grammar
+        (kernels.py:461-505), restricted to ``SP_k{k}`` (raw counts) and ``MM_k{k}_m{m}``
+        (normalised, as get_mismatch_K returns it); anything else raises ValueError."""
+        tok = str(method).split('_')
+        try:
+            if tok[0] == 'SP' and len(tok) == 2 and tok[1][:1] == 'k':
+                p = P.make(L.KMG_SPECTRUM, k=int(tok[1][1:]))
+            elif tok[0] == 'MM' and len(tok) == 3 and tok[1][:1] == 'k' and tok[2][:1] == 'm':
+                p = P.make(L.KMG_MISMATCH, k=int(tok[1][1:]), m=int(tok[2][1:]), window=101,
+                           normalize=1)
+            else:
+                raise ValueError
+        except ValueError:
+            raise ValueError(f"scorer: method {method!r} is not SP_k{{k}} or MM_k{{k}}_m{{m}}") from None
+        seqs = list(seqs)
+        mm = p.kind == L.KMG_MISMATCH
+        self._check_scored(seqs, mm)
+        codes, lens = E.encode(seqs)
+        return EngineScorer(self, self.ctx.scorer(p, codes, lens, coef), mm)
+
+    def _check_scored(self, seqs, mm):
+        """Mismatch rows: get_mismatch_K's own refusals (see ``mismatch``)."""
+        if not mm:
+            return
+        self._require_acgt(seqs)
+        short = [len(s) for s in seqs if len(s) < 101]
+        if short:
+            raise ValueError(f"operands could not be broadcast together (sequence of length "
+                             f"{short[0]} < 101)")
+
     # ------------------------------------------------------------------ feature maps
     def features(self, kind, seqs, k, cols, m=0, g=0):
         """float64 [len(seqs), len(cols)]: the reference's per-sequence feature map of each
@@ -211,6 +244,24 @@ class GramEngine:
     def center(self, K):
         """center_K (kernels.py:387-395)."""
         return self.ctx.center(np.ascontiguousarray(K, dtype=np.float64))
+
+
+class EngineScorer:
+    """What ``GramEngine.scorer`` returns: ``score(seqs, bias)`` on strings."""
+
+    def __init__(self, engine, scorer, mm):
+        self.engine, self._s, self._mm = engine, scorer, mm
+
+    def score(self, seqs, bias=0.0):
+        seqs = list(seqs)
+        if not seqs:
+            return np.zeros(0, dtype=np.float64)
+        self.engine._check_scored(seqs, self._mm)
+        codes, lens = E.encode(seqs)
+        return self._s.score(codes, lens, bias)
+
+    def close(self):
+        self._s.close()
 
 
 def gappy_reference_errors(n_x, k, g, window=101):

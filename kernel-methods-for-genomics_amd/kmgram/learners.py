@@ -30,6 +30,20 @@ def _labels(y):
     return np.asarray(y.loc[:, "Bound"] if hasattr(y, "loc") else y)
 
 
+class _ModelScorer:
+    """A fitted learner's support vectors and intercept behind ``decision_function`` /
+    ``predict`` on raw sequences (``_GramLearner.scorer``)."""
+
+    def __init__(self, scorer, b):
+        self._scorer, self.b = scorer, b
+
+    def decision_function(self, seqs):
+        return self._scorer.score(seqs, bias=self.b)
+
+    def predict(self, seqs):
+        return np.sign(self.decision_function(seqs))
+
+
 class _GramLearner:
     """Shared fit/predict bookkeeping (identical in KRR.py, KLR.py and SVM.py)."""
 
@@ -62,6 +76,18 @@ class _GramLearner:
     def predict(self, X):
         """sign(sum_sv a_s K[s, i] + b) for every row of X (KRR.py:43-56)."""
         return np.sign(self.decision_function(X))
+
+    def scorer(self, seqs, method):
+        """The fitted model as a device scorer for sequences that are not rows of ``K``
+        (GramEngine.scorer): ``seqs`` are the sequences of the rows of ``self.K`` in the
+        order of ``self.ID`` and ``method`` the kernel K was built with (``SP_k{k}`` or
+        ``MM_k{k}_m{m}``).  The result has ``decision_function(new_seqs)`` and
+        ``predict(new_seqs)``, the counterparts of the methods above (KRR.py:43-56)."""
+        seqs = list(seqs)
+        if len(seqs) != len(self.ID):
+            raise ValueError(f"{len(seqs)} sequences for the {len(self.ID)} rows of K")
+        sv = default_engine().scorer(method, [seqs[i] for i in self.idx_sv], self.a)
+        return _ModelScorer(sv, float(self.b))
 
     def score(self, pred, y):
         """Accuracy of -1/1 predictions (KRR.py:58-66)."""
