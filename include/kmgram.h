@@ -54,10 +54,24 @@ enum {
   KMG_WDS = 4,        /* get_WDShifts_K   kernels.py:138-155 */
   KMG_SUBSTRING = 5,  /* get_string_K     kernels.py:367-382 */
   KMG_LOCALALIGN = 6, /* get_LA_K         kernels.py:273-302 */
-  KMG_GAPPY = 7       /* get_gappy_K      kernels.py:436-455 (la_mode KMG_MODE_REFERENCE: the
+  KMG_GAPPY = 7,      /* get_gappy_K     kernels.py:436-455 (la_mode KMG_MODE_REFERENCE: the
                          reference's behaviour, defined for k=1,g=0 -- every other (k,g) raises
                          there under numpy 2; KMG_MODE_INTENDED: any 0 <= g < k,
                          k <= 15, k-g <= 8) */
+  KMG_GKM = 8         /* gapped k-mer kernel of gkm-SVM / LS-GKM (Ghandi, Lee, Mohammad-Noori, Beer,
+                         PLoS Comput Biol 2014; no reference counterpart):
+                           K(x, y) = sum_{a, b} h[ham(x[a:a+l], y[b:b+l])]
+                           h[m] = C(l - m, k) for m <= d, 0 otherwise
+                         over the all-ACGT words of length l of the whole rows (a word holding any
+                         other symbol is not counted), k informative positions, truncation d.
+                         kmg_params: k = l (1..16), g = l - k (0..l-1, the gappy family's sense),
+                         m = d (0..g); anything else is KMG_EINVAL, as is normalize = 1 into
+                         KMG_I32.  A row of more than 256 words is KMG_EUNSUPPORTED (the all-pairs
+                         Hamming bound), so every raw value is an exact integer < 2^31.  Served
+                         by kmg_gram, kmg_gram_device and kmg_gram_to_host; kmg_gram_device_cols,
+                         kmg_gram_blocks, kmg_scorer_create and kmg_features* return
+                         KMG_EUNSUPPORTED.  At l = 16 the word T^16 shares the 32 bits of the
+                         invalid-word marker and is not counted. */
 };
 
 /* output element types */
@@ -80,11 +94,11 @@ enum { KMG_MODE_REFERENCE = 0 /* the reference's behaviour (GP: k=1,g=0 only) */
 
 typedef struct kmg_params {
   int32_t kind;      /* KMG_* family */
-  int32_t k;         /* SP/MM/GP k-mer length; SS subsequence length */
-  int32_t m;         /* MM maximal mismatches */
+  int32_t k;         /* SP/MM/GP k-mer length; SS subsequence length; GKM word length l */
+  int32_t m;         /* MM maximal mismatches; GKM truncation d (0 <= m <= g) */
   int32_t d;         /* WD/WDS maximal degree */
   int32_t S;         /* WDS maximal shift */
-  int32_t g;         /* GP gap */
+  int32_t g;         /* GP gap; GKM l - (informative positions) */
   int32_t window;    /* MM/GP: fixed window the reference hard-codes (101, kernels.py:171,430) */
   int32_t normalize; /* 1: fused normalize_K epilogue (kernels.py:398-415) */
   int32_t smith;     /* LA: 1 = Smith_Waterman max form */
@@ -348,6 +362,7 @@ int kmg_stream(kmg_ctx *ctx, void **hip_stream);
  * "pack" (2-bit packing of the input), "slots" (mismatch slot / pair tables, neighbourhood
  * lists), "lists" (neighbourhood-list sizes and starts), "combine",
  * "vtab" / "butterfly" / "score" (kmg_scorer_*: weight table, Hamming DP, query scoring),
+ * "gkm" (the tiled gapped k-mer Gram kernel, inside the call's "gram" stage),
  * "solve", "memset", "gather" (the RCCL all-gathers of kmg_gram_blocks, timed on their own
  * stream), "unpack" (round-slab assembly), "mirror" (lower block triangle of a full square
  * mismatch K built by its upper block triangle).

@@ -94,12 +94,12 @@ const char *kStageNames[] = {"count",   "scan",     "place", "fine",    "diag",
                              "gram",    "extract",  "pack",  "features", "combine",
                              "solve",   "slots",    "memset", "gather", "unpack",
                              "mirror",  "lists",    "nbfill", "vtab",   "butterfly",
-                             "score"};
-constexpr int kNumStages = 21;
+                             "score",   "gkm"};
+constexpr int kNumStages = 22;
 enum {
   ST_COUNT, ST_SCAN, ST_PLACE, ST_FINE, ST_DIAG, ST_GRAM, ST_EXTRACT, ST_PACK, ST_FEATURES,
   ST_COMBINE, ST_SOLVE, ST_SLOTS, ST_MEMSET, ST_GATHER, ST_UNPACK, ST_MIRROR, ST_LISTS,
-  ST_NBFILL, ST_VTAB, ST_BUTTERFLY, ST_SCORE
+  ST_NBFILL, ST_VTAB, ST_BUTTERFLY, ST_SCORE, ST_GKM
 };
 
 // Tuning knobs: read from the environment once per context (kmg_create) and again only on
@@ -1496,6 +1496,81 @@ int gram_device(kmg_ctx *c, const kmg_params *p, const uint8_t *d_codes, const i
                                   c->stream);
       });
     }
+    case KMG_GKM: {
+      // gapped k-mer kernel (kmg_gkm.hip): K = sum_{a,b} h[ham(x_a, y_b)] over the all-ACGT
+      // l-letter words of the whole rows, h[m] = C(l - m, l - g) for m <= d
+      const int l = p->k, gap = p->g, d = p->m;
+      if (l < 1 || l > 16) return fail(KMG_EINVAL, "gkm: word length l = %d outside 1..16", l);
+      if (gap < 0 || gap > l - 1)
+        return fail(KMG_EINVAL, "gkm: g = %d outside 0..l-1 (l = %d)", gap, l);
+      if (d < 0 || d > gap) return fail(KMG_EINVAL, "gkm: truncation m = %d outside 0..g (g = %d)", d, gap);
+      if (dt == KMG_I32 && p->normalize)
+        return fail(KMG_EINVAL, "normalised output needs a floating dtype");
+      IndexGeom g{};
+      g.k = l;
+      g.n = n;
+      g.window = 0;  // the whole row
+      g.pmax = maxlen - l + 1 > 0 ? maxlen - l + 1 : 1;
+      g.copies = 1;
+      g.nkeys = 1;
+      g.chunk = (int)(n > 0 ? n : 1);
+      g.nchunks = 1;
+      if (g.pmax > 256)
+        return fail(KMG_EUNSUPPORTED, "gkm: rows of more than 256 words (%d) are past the all-pairs "
+                    "Hamming path", g.pmax);
+      GkmWeights wt{};
+      {
+        int64_t binom[17][17] = {};
+        for (int a = 0; a <= 16; ++a) {
+          binom[a][0] = 1;
+          for (int b = 1; b <= a; ++b) binom[a][b] = binom[a - 1][b - 1] + (b <= a - 1 ? binom[a - 1][b] : 0);
+        }
+        for (int m = 0; m <= d; ++m) wt.h[m] = (int32_t)binom[l - m][l - gap];
+      }
+      const int cw = packed_cw(ldc), mw = packed_mw(ldc);
+      KMG_TRY(c->packed.ensure(sizeof(uint32_t) * (size_t)std::max<int64_t>(1, n) * (cw + mw)));
+      const Packed pkd{c->packed.as<uint32_t>(), (int64_t)(cw + mw), cw};
+      KMG_TRY(c->kmers.ensure(sizeof(uint32_t) * (size_t)(n * g.pmax > 0 ? n * g.pmax : 1)));
+      {
+        StageTimer t(c, ST_PACK);
+        KMG_HIP(launch_pack(d_codes, d_lens, n, ldc, 0, c->packed.as<uint32_t>(), c->stream));
+      }
+      {
+        StageTimer t(c, ST_EXTRACT);
+        KMG_HIP(launch_extract(g, pkd, c->kmers.as<uint32_t>(), c->stream));
+      }
+      if (p->normalize) {
+        KMG_TRY(c->diagv.ensure(sizeof(double) * (size_t)(n > 0 ? n : 1)));
+        KMG_TRY(c->dsq.ensure(sizeof(double) * (size_t)(n > 0 ? n : 1)));
+        StageTimer t(c, ST_DIAG);
+        KMG_HIP(launch_gkm_diag(c->kmers.as<uint32_t>(), g.pmax, l, n, wt, c->diagv.as<double>(),
+                                c->dsq.as<double>(), c->stream));
+        o.normalize = 1;
+        o.diagv = c->diagv.as<double>();
+        o.dsq = c->dsq.as<double>();
+      }
+      // the symmetric form (upper block triangle, every off-diagonal tile stored twice) exactly
+      // when one range covers all n rows; otherwise every tile of the range, rows split at the
+      // launch's tile limit
+      const bool square = ranges.size() == 1 && ranges[0].row0 == 0 && ranges[0].row1 == n &&
+                          ranges[0].col_lo == 0 && n > 0;
+      const bool sym = square && gkm_tiles(n, n, true) < KMG_GKM_MAX_TILES;
+      const int64_t tiles_c = (n + 15) / 16;
+      const int64_t max_rows = std::max<int64_t>(16, (KMG_GKM_MAX_TILES - 1) / std::max<int64_t>(1, tiles_c) * 16);
+      return each_range(c, ranges, o, after, [&](int64_t r0, int64_t r1, const OutSpec &oq) {
+        StageTimer t(c, ST_GKM);
+        if (sym)
+          return launch_gram_gkm(c->kmers.as<uint32_t>(), g.pmax, l, n, r0, r1, true, wt, oq, c->stream);
+        for (int64_t r = r0; r < r1; r += max_rows) {
+          OutSpec os = oq;
+          os.out = (char *)oq.out + (size_t)(r - r0) * oq.ld * dtype_size(dt);
+          hipError_t e = launch_gram_gkm(c->kmers.as<uint32_t>(), g.pmax, l, n, r, std::min(r1, r + max_rows),
+                                         false, wt, os, c->stream);
+          if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+      });
+    }
     default:
       return fail(KMG_EINVAL, "unknown kernel kind %d", p->kind);
   }
@@ -1646,6 +1721,8 @@ static int features_impl(kmg_ctx *c, const kmg_params *p, const uint8_t *codes, 
       window = p->window > 0 ? p->window : 101;
       binary = 1;
       break;
+    case KMG_GKM:
+      return fail(KMG_EUNSUPPORTED, "features: the gkm kernel (KMG_GKM) has no explicit feature map here");
     default:
       return fail(KMG_EUNSUPPORTED, "features: spectrum, mismatch or gappy only");
   }
@@ -1733,6 +1810,8 @@ int kmg_gram_device_cols(kmg_ctx *c, const kmg_params *p, const uint8_t *d_codes
   if (!c) return fail(KMG_EINVAL, "ctx is NULL");
   std::lock_guard<std::mutex> lk(c->mu);
   KMG_TRY(check_params(p, n, ldc, out_dtype));
+  if (p->kind == KMG_GKM)
+    return fail(KMG_EUNSUPPORTED, "column blocks: the gkm kernel (KMG_GKM) is built by rows only");
   if (col0 < 0 || col1 > n || col0 >= col1) return fail(KMG_EINVAL, "bad column range");
   KMG_HIP(hipSetDevice(c->device));
   return gram_device(c, p, d_codes, d_lens, (int)ldc, n, ldc, {RowRange{0, n, d_out}},
@@ -1752,6 +1831,7 @@ struct kmg_scorer {
 
 static int scorer_check_params(const kmg_params *p) {
   if (!p) return fail(KMG_EINVAL, "params is NULL");
+  if (p->kind == KMG_GKM) return fail(KMG_EUNSUPPORTED, "scorer: the gkm kernel (KMG_GKM) has no table scorer");
   if (p->kind != KMG_SPECTRUM && p->kind != KMG_MISMATCH)
     return fail(KMG_EUNSUPPORTED, "scorer: spectrum or mismatch only (kind %d)", p->kind);
   if (p->k < 1 || p->k > 12) return fail(KMG_EUNSUPPORTED, "scorer: 1 <= k <= 12 (k = %d)", p->k);
@@ -2156,6 +2236,9 @@ int kmg_gram_blocks(kmg_ctx *c, const kmg_params *p, const uint8_t *d_codes,
   if (!c) return fail(KMG_EINVAL, "ctx is NULL");
   std::lock_guard<std::mutex> lk(c->mu);
   KMG_TRY(check_params(p, n, ldc, out_dtype));
+  if (p->kind == KMG_GKM)
+    return fail(KMG_EUNSUPPORTED, "kmg_gram_blocks: the gkm kernel (KMG_GKM) is not dealt in blocks; "
+                "shard its rows with kmg_gram_device");
   if (gather == 5 || gather == 6)
     return gram_colblocks_impl(c, p, d_codes, d_lens, n, ldc, out_dtype, d_out, ld_out, nranks,
                                rank, block, gather);

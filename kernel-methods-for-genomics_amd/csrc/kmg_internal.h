@@ -277,6 +277,24 @@ hipError_t launch_gram_hamming(const IndexGeom &g, const uint32_t *kmers, int64_
 hipError_t launch_diag_hamming(const IndexGeom &g, const Packed &pk, const int64_t *wtab,
                                int max_dist, double *diagv, double *dsq, hipStream_t s);
 
+// ---------------------------------------------------------------- gkm (kmg_gkm.hip)
+// gapped k-mer kernel: K = sum_{a,b} h[ham(x_a, y_b)] over the [n][pmax] words of
+// launch_extract (window 0: the whole row), pmax <= 256, word length l <= 16
+struct GkmWeights {
+  int32_t h[17];  // h[m] = C(l - m, k) for m <= d, else 0 (exact integers, host-computed)
+};
+// tiles of one launch (16 x 16 sequences each) and their limit: 256 threads a tile within
+// the 32-bit AQL grid size; the caller splits rows so every launch stays below it
+#define KMG_GKM_MAX_TILES ((int64_t)1 << 24)
+int64_t gkm_tiles(int64_t n, int64_t rows, bool sym);
+// rows [row0, row1) x all n columns at o.out; sym (row0 = 0, row1 = n only): the upper block
+// triangle is computed and every off-diagonal tile stored twice
+hipError_t launch_gram_gkm(const uint32_t *words, int pmax, int l, int64_t n, int64_t row0,
+                           int64_t row1, bool sym, const GkmWeights &wt, const OutSpec &o,
+                           hipStream_t s);
+hipError_t launch_gkm_diag(const uint32_t *words, int pmax, int l, int64_t n, const GkmWeights &wt,
+                           double *diagv, double *dsq, hipStream_t s);
+
 // ---------------------------------------------------------------- scorer (kmg_score.hip)
 // V[key] = sum over the key's posting lists (exact index, copies = 1, every chunk) of the
 // 128-bit fixed-point weights fix[2 row], fix[2 row + 1] (low, high word), rounded once to

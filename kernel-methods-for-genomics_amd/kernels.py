@@ -21,8 +21,8 @@ from kmgram.params import beta, delta  # noqa: F401  (reference helpers, kernels
 
 __all__ = [
     "get_spectrum_K", "get_WD_K", "get_WDShifts_K", "get_mismatch_K", "get_LA_K",
-    "get_string_K", "get_gappy_K", "center_K", "normalize_K", "select_method", "beta",
-    "delta", "letter_to_num", "format", "S", "get_WD_d", "get_WDShifts_d", "K_k",
+    "get_string_K", "get_gappy_K", "get_gkm_K", "center_K", "normalize_K", "select_method",
+    "beta", "delta", "letter_to_num", "format", "S", "get_WD_d", "get_WDShifts_d", "K_k",
     "affine_align", "Smith_Waterman", "get_phi_u", "get_phi_km", "gappy_k", "B_k", "rec",
 ]
 
@@ -68,6 +68,13 @@ def get_string_K(X, lbda, k):
 def get_gappy_K(X, k, g):
     """Gappy kernel GP(k, g) (kernels.py:436-455)."""
     return _eng().gappy(_seqs(X), k, g)
+
+
+def get_gkm_K(X, l, k, d=None):
+    """Gapped k-mer kernel of gkm-SVM (word length l, k informative positions, truncation d;
+    d=None is min(3, l - k)), normalised.  Not in the reference: ``select_method`` has no
+    method string for it."""
+    return _eng().gkm(_seqs(X), l, k, d)
 
 
 # ----------------------------------------------------------------------- helpers

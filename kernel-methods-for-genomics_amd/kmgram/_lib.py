@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("KMGRAM_LIB") or os.path.join(os.path.dirname(_HERE), 
 (KMG_OK, KMG_EINVAL, KMG_EUNSUPPORTED, KMG_EHIP, KMG_ENOMEM, KMG_ERCCL, KMG_ENODEV,
  KMG_ESINGULAR, KMG_EINTERNAL) = range(9)
 KMG_SPECTRUM, KMG_MISMATCH, KMG_WD, KMG_WDS, KMG_SUBSTRING, KMG_LOCALALIGN, KMG_GAPPY = range(1, 8)
+KMG_GKM = 8  # gapped k-mer kernel of gkm-SVM / LS-GKM (include/kmgram.h)
 KMG_I32, KMG_F32, KMG_F64 = 1, 2, 3
 KMG_LA_REFERENCE, KMG_LA_INTENDED = 0, 1
 KMG_MODE_REFERENCE, KMG_MODE_INTENDED = 0, 1  # GP semantics (include/kmgram.h)

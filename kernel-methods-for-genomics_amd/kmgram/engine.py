@@ -6,6 +6,7 @@ Each method takes a list of sequences (str) and returns the full symmetric
 encodes sequences, validates reference-visible error cases and copies results back.
 """
 import os
+import re
 import threading
 
 import numpy as np
@@ -177,6 +178,24 @@ class GramEngine:
         for s in seqs:
             gappy_reference_errors(len(s), k, g)
         return self._run(P.make(L.KMG_GAPPY, k=k, g=g, window=101), seqs)
+
+    def gkm(self, seqs, l, k, d=None, normalize=True, out_dtype=L.KMG_F64):
+        """Gapped k-mer kernel of gkm-SVM / LS-GKM (Ghandi et al. 2014; no reference
+        counterpart): K_ij = sum_{a,b} h[ham(x_i[a:a+l], x_j[b:b+l])], h[m] = C(l - m, k) for
+        m <= d, over the all-ACGT words of the whole rows (a word holding any other character
+        is not counted); d=None is min(3, l - k).  normalize=True applies normalize_K, and a
+        sequence without a valid word (its K_ii would be 0) raises ValueError."""
+        p = P.gkm(l, k, d, normalize)
+        seqs = list(seqs)
+        if normalize:
+            if out_dtype == L.KMG_I32:
+                raise ValueError("gkm: normalised output needs a floating dtype")
+            word = re.compile("[ACGT]{%d}" % int(l))
+            for i, s in enumerate(seqs):
+                if not word.search(s):
+                    raise ValueError(f"gkm: sequence {i} has no all-ACGT word of length {int(l)}; "
+                                     "its diagonal would be 0 under normalize=True")
+        return self._run(p, seqs, out_dtype)
 
     # ------------------------------------------------------------------ scoring
     def scorer(self, method, seqs, coef):

@@ -36,6 +36,28 @@ def mismatch_weights(k, m):
     return w
 
 
+def gkm_weights(l, k, d):
+    """h[m] = C(l - m, k) for m <= d, else 0 (m = 0..l): the gapped k-mers -- l-mers with k
+    informative positions -- two words at Hamming distance m share (gkm-SVM, Ghandi et al.
+    2014), truncated at d mismatches.  The device table is built from the same integers."""
+    return [comb(l - m, k) if m <= d else 0 for m in range(l + 1)]
+
+
+def gkm(l, k, d=None, normalize=True):
+    """KmgParams of the gapped k-mer kernel: word length l (1..16), k informative positions
+    (1..l), truncation d (0..l - k; None = min(3, l - k), gkm-SVM's default).  The struct
+    carries them as k = l, g = l - k, m = d."""
+    l, k = int(l), int(k)
+    if not 1 <= l <= 16:
+        raise ValueError(f"gkm: word length l={l} outside 1..16")
+    if not 1 <= k <= l:
+        raise ValueError(f"gkm: k={k} informative positions outside 1..l (l={l})")
+    d = min(3, l - k) if d is None else int(d)
+    if not 0 <= d <= l - k:
+        raise ValueError(f"gkm: truncation d={d} outside 0..l-k (l-k={l - k})")
+    return make(L.KMG_GKM, k=l, g=l - k, m=d, normalize=1 if normalize else 0)
+
+
 def make(kind, **kw):
     """Fill a KmgParams struct."""
     p = L.KmgParams()
