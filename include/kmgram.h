@@ -71,7 +71,8 @@ enum {
                          by kmg_gram, kmg_gram_device and kmg_gram_to_host; kmg_gram_device_cols,
                          kmg_gram_blocks, kmg_scorer_create and kmg_features* return
                          KMG_EUNSUPPORTED.  At l = 16 the word T^16 shares the 32 bits of the
-                         invalid-word marker and is not counted. */
+                         invalid-word marker and is not counted.  kmg_gkm_cross* lift both
+                         limits (rows of any length, T^16 counted) for rectangular blocks. */
 };
 
 /* output element types */
@@ -140,6 +141,31 @@ int kmg_gram(kmg_ctx *ctx, const kmg_params *p, const uint8_t *codes, const int3
 int kmg_gram_device(kmg_ctx *ctx, const kmg_params *p, const uint8_t *d_codes,
                     const int32_t *d_lens, int64_t n, int64_t ldc, int64_t row0, int64_t row1,
                     int32_t out_dtype, void *d_out, int64_t ld_out);
+
+/*
+ * Rectangular gapped k-mer block between two sequence sets, rows of any length:
+ *   out[i][j] = sum_{a, b} h[ham(A_i[a:a+l], B_j[b:b+l])]        (na x nb, row stride ld_out)
+ * with KMG_GKM's h, parameters and word rules (p->kind must be KMG_GKM; any other kind is
+ * KMG_EUNSUPPORTED), except that no row length is refused and T^16 counts like any other word.
+ * This is the block K(queries x support vectors) of f(q) = sum_t beta_t K(q, x_t), and with
+ * A = B the square gkm Gram of rows past the 256 words of the Gram entry points.  Word matches
+ * are int8 MFMA products of one-hot word matrices (kmg_gkmx.hip); the raw values are exact
+ * integers.  p->normalize = 1: out[i][j] / (sqrt(K(A_i, A_i)) * sqrt(K(B_j, B_j))), one division
+ * (a row without a word gives NaN; no unit diagonal is filled in: the block has none).
+ * With P_a, P_b the word counts of the longest rows: P_a P_b h[0] >= 2^53 is KMG_EUNSUPPORTED;
+ * KMG_I32 with P_a P_b h[0] >= 2^31, or with normalize = 1, is KMG_EINVAL; na = 0 or nb = 0
+ * returns KMG_OK and writes nothing.  All of it is checked before any allocation or launch.
+ * Host buffers in and out, synchronous.
+ */
+int kmg_gkm_cross(kmg_ctx *ctx, const kmg_params *p, const uint8_t *codes_a, const int32_t *lens_a,
+                  int64_t na, int64_t ldc_a, const uint8_t *codes_b, const int32_t *lens_b,
+                  int64_t nb, int64_t ldc_b, int32_t out_dtype, void *out, int64_t ld_out);
+/* The same on device pointers (rows up to ldc_a / ldc_b symbols bound the checks above), on
+ * the context stream, without synchronising. */
+int kmg_gkm_cross_device(kmg_ctx *ctx, const kmg_params *p, const uint8_t *d_codes_a,
+                         const int32_t *d_lens_a, int64_t na, int64_t ldc_a,
+                         const uint8_t *d_codes_b, const int32_t *d_lens_b, int64_t nb,
+                         int64_t ldc_b, int32_t out_dtype, void *d_out, int64_t ld_out);
 
 /*
  * Device-resident column block: K[i][col0 + j] for every row i in [0, n) and j in
@@ -363,6 +389,7 @@ int kmg_stream(kmg_ctx *ctx, void **hip_stream);
  * lists), "lists" (neighbourhood-list sizes and starts), "combine",
  * "vtab" / "butterfly" / "score" (kmg_scorer_*: weight table, Hamming DP, query scoring),
  * "gkm" (the tiled gapped k-mer Gram kernel, inside the call's "gram" stage),
+ * "gkmx" (the rectangular gkm kernel of kmg_gkm_cross*; its diagonals count under "diag"),
  * "solve", "memset", "gather" (the RCCL all-gathers of kmg_gram_blocks, timed on their own
  * stream), "unpack" (round-slab assembly), "mirror" (lower block triangle of a full square
  * mismatch K built by its upper block triangle).

@@ -94,12 +94,12 @@ const char *kStageNames[] = {"count",   "scan",     "place", "fine",    "diag",
                              "gram",    "extract",  "pack",  "features", "combine",
                              "solve",   "slots",    "memset", "gather", "unpack",
                              "mirror",  "lists",    "nbfill", "vtab",   "butterfly",
-                             "score",   "gkm"};
-constexpr int kNumStages = 22;
+                             "score",   "gkm",      "gkmx"};
+constexpr int kNumStages = 23;
 enum {
   ST_COUNT, ST_SCAN, ST_PLACE, ST_FINE, ST_DIAG, ST_GRAM, ST_EXTRACT, ST_PACK, ST_FEATURES,
   ST_COMBINE, ST_SOLVE, ST_SLOTS, ST_MEMSET, ST_GATHER, ST_UNPACK, ST_MIRROR, ST_LISTS,
-  ST_NBFILL, ST_VTAB, ST_BUTTERFLY, ST_SCORE, ST_GKM
+  ST_NBFILL, ST_VTAB, ST_BUTTERFLY, ST_SCORE, ST_GKM, ST_GKMX
 };
 
 // Tuning knobs: read from the environment once per context (kmg_create) and again only on
@@ -243,6 +243,8 @@ struct kmg_ctx {
   DevBuf chk;                       // KMG_CHECK: validation flag + first offending list
   DevBuf cb_scratch;                // column-block assembly: one rank's K[:, C_q] (n x block)
   DevBuf sc_fix, sc_tab;            // kmg_scorer_create: fixed-point weights, the DP tables
+  DevBuf gx_words_b, gx_bits;       // kmg_gkm_cross: side B's words (side A's are in kmers),
+                                    // the validity bits of A, then B
   Tuning tune;
   DevBuf cmb_k, cmb_ptrs, cmb_vec, cmb_out, cmb_tmp;  // combination consumers (host path)
   DevBuf sv_mat, sv_vec, sv_info;  // dense learners: factorised system, vectors, info/ipiv
@@ -337,6 +339,26 @@ void mismatch_weights(int k, int m, int64_t *w) {
     }
     w[d] = tot;
   }
+}
+
+// KMG_GKM's parameter rules (kmg_gram* and kmg_gkm_cross*) and its weights h[m] = C(l - m, l - g)
+// for m <= d: exact integers, passed to the kernels by value
+int gkm_check(const kmg_params *p, int32_t dt, GkmWeights &wt) {
+  const int l = p->k, gap = p->g, d = p->m;
+  if (l < 1 || l > 16) return fail(KMG_EINVAL, "gkm: word length l = %d outside 1..16", l);
+  if (gap < 0 || gap > l - 1)
+    return fail(KMG_EINVAL, "gkm: g = %d outside 0..l-1 (l = %d)", gap, l);
+  if (d < 0 || d > gap) return fail(KMG_EINVAL, "gkm: truncation m = %d outside 0..g (g = %d)", d, gap);
+  if (dt == KMG_I32 && p->normalize)
+    return fail(KMG_EINVAL, "normalised output needs a floating dtype");
+  int64_t binom[17][17] = {};
+  for (int a = 0; a <= 16; ++a) {
+    binom[a][0] = 1;
+    for (int b = 1; b <= a; ++b) binom[a][b] = binom[a - 1][b - 1] + (b <= a - 1 ? binom[a - 1][b] : 0);
+  }
+  wt = GkmWeights{};
+  for (int m = 0; m <= d; ++m) wt.h[m] = (int32_t)binom[l - m][l - gap];
+  return KMG_OK;
 }
 
 int check_params(const kmg_params *p, int64_t n, int64_t ldc, int32_t dt) {
@@ -1499,13 +1521,9 @@ int gram_device(kmg_ctx *c, const kmg_params *p, const uint8_t *d_codes, const i
     case KMG_GKM: {
       // gapped k-mer kernel (kmg_gkm.hip): K = sum_{a,b} h[ham(x_a, y_b)] over the all-ACGT
       // l-letter words of the whole rows, h[m] = C(l - m, l - g) for m <= d
-      const int l = p->k, gap = p->g, d = p->m;
-      if (l < 1 || l > 16) return fail(KMG_EINVAL, "gkm: word length l = %d outside 1..16", l);
-      if (gap < 0 || gap > l - 1)
-        return fail(KMG_EINVAL, "gkm: g = %d outside 0..l-1 (l = %d)", gap, l);
-      if (d < 0 || d > gap) return fail(KMG_EINVAL, "gkm: truncation m = %d outside 0..g (g = %d)", d, gap);
-      if (dt == KMG_I32 && p->normalize)
-        return fail(KMG_EINVAL, "normalised output needs a floating dtype");
+      const int l = p->k;
+      GkmWeights wt{};
+      KMG_TRY(gkm_check(p, dt, wt));
       IndexGeom g{};
       g.k = l;
       g.n = n;
@@ -1518,15 +1536,6 @@ int gram_device(kmg_ctx *c, const kmg_params *p, const uint8_t *d_codes, const i
       if (g.pmax > 256)
         return fail(KMG_EUNSUPPORTED, "gkm: rows of more than 256 words (%d) are past the all-pairs "
                     "Hamming path", g.pmax);
-      GkmWeights wt{};
-      {
-        int64_t binom[17][17] = {};
-        for (int a = 0; a <= 16; ++a) {
-          binom[a][0] = 1;
-          for (int b = 1; b <= a; ++b) binom[a][b] = binom[a - 1][b - 1] + (b <= a - 1 ? binom[a - 1][b] : 0);
-        }
-        for (int m = 0; m <= d; ++m) wt.h[m] = (int32_t)binom[l - m][l - gap];
-      }
       const int cw = packed_cw(ldc), mw = packed_mw(ldc);
       KMG_TRY(c->packed.ensure(sizeof(uint32_t) * (size_t)std::max<int64_t>(1, n) * (cw + mw)));
       const Packed pkd{c->packed.as<uint32_t>(), (int64_t)(cw + mw), cw};
@@ -1637,7 +1646,7 @@ int kmg_destroy(kmg_ctx *c) {
                     &c->tri_stage, &c->tri_scratch, &c->dense_tiles, &c->ovf, &c->slabs,
                     &c->gcoef, &c->feat32, &c->k32, &c->ft_cols,
                     &c->nb_seg, &c->nb_use, &c->nb_lines, &c->chk, &c->cb_scratch,
-                    &c->sc_fix, &c->sc_tab};
+                    &c->sc_fix, &c->sc_tab, &c->gx_words_b, &c->gx_bits};
   for (DevBuf *b : bufs) b->release();
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
   if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
@@ -1802,6 +1811,153 @@ int kmg_gram_device(kmg_ctx *c, const kmg_params *p, const uint8_t *d_codes,
   // max(lens) <= ldc (checked in the host path).  maxlen = ldc bounds every kernel.
   return gram_device(c, p, d_codes, d_lens, (int)ldc, n, ldc, {RowRange{row0, row1, d_out}},
                      out_dtype, ld_out);
+}
+
+// kmg_gkm_cross*: what both entry points check before anything is allocated or launched
+static int gkm_cross_check(const kmg_params *p, int64_t na, int64_t ldc_a, int64_t nb, int64_t ldc_b,
+                           int32_t dt, GkmWeights &wt) {
+  KMG_TRY(check_params(p, na, ldc_a, dt));
+  KMG_TRY(check_params(p, nb, ldc_b, dt));
+  if (p->kind != KMG_GKM)
+    return fail(KMG_EUNSUPPORTED, "gkm cross: kernel kind %d is not KMG_GKM", p->kind);
+  return gkm_check(p, dt, wt);
+}
+
+// ... and the bounds of a call whose rows are at most maxlen_a / maxlen_b symbols long
+static int gkm_cross_bounds(const kmg_params *p, const GkmWeights &wt, int maxlen_a, int64_t na,
+                            int maxlen_b, int64_t nb, int32_t dt) {
+  const int l = p->k;
+  const int pa = std::max(1, maxlen_a - l + 1), pb = std::max(1, maxlen_b - l + 1);
+  const double two53 = 9007199254740992.0, h0 = (double)wt.h[0];
+  // every raw value is an exact integer in float64 (and in int32 where that is the output)
+  const double top = (double)pa * (double)pb * h0;
+  const double dtop = (double)std::max(pa, pb) * (double)std::max(pa, pb) * h0;
+  if (top >= two53 || (p->normalize && dtop >= two53))
+    return fail(KMG_EUNSUPPORTED, "gkm cross: %d x %d words a pair can reach 2^53", pa, pb);
+  if (dt == KMG_I32 && top >= 2147483648.0)
+    return fail(KMG_EINVAL, "gkm cross: %d x %d words a pair can pass int32; use a floating dtype",
+                pa, pb);
+  const int nba = gkmx_blocks(pa), nbb = gkmx_blocks(pb);
+  const int64_t limit = KMG_GKM_MAX_TILES * 8;  // rows a launch grid reaches, words an extract
+  if (na >= limit || nb >= limit || (double)na * nba * 32 >= (double)limit * 32 ||
+      (double)nb * nbb * 32 >= (double)limit * 32)
+    return fail(KMG_EUNSUPPORTED, "gkm cross: %lld x %lld rows of %d / %d words are past one call",
+                (long long)na, (long long)nb, pa, pb);
+  return KMG_OK;
+}
+
+// device rows of both sides -> words + validity bits, sqrt(K_ii) of both sides under
+// normalisation (the same kernel over the pairs (i, i)), then the rectangular kernel
+// (kmg_gkmx.hip); na, nb > 0 and gkm_cross_bounds has passed
+static int gkm_cross_device(kmg_ctx *c, const kmg_params *p, const GkmWeights &wt,
+                            const uint8_t *d_ca, const int32_t *d_la, int maxlen_a, int64_t na,
+                            int64_t ldc_a, const uint8_t *d_cb, const int32_t *d_lb, int maxlen_b,
+                            int64_t nb, int64_t ldc_b, int32_t dt, void *d_out, int64_t ld) {
+  c->last_call_first = (int)c->ev_log.size();
+  const int l = p->k;
+  const int pa = std::max(1, maxlen_a - l + 1), pb = std::max(1, maxlen_b - l + 1);
+  const int nba = gkmx_blocks(pa), nbb = gkmx_blocks(pb);
+
+  const int64_t ldp_a = packed_cw(ldc_a) + packed_mw(ldc_a), ldp_b = packed_cw(ldc_b) + packed_mw(ldc_b);
+  KMG_TRY(c->packed.ensure(sizeof(uint32_t) * (size_t)std::max(na * ldp_a, nb * ldp_b)));
+  KMG_TRY(c->kmers.ensure(sizeof(uint32_t) * (size_t)na * nba * 32));
+  KMG_TRY(c->gx_words_b.ensure(sizeof(uint32_t) * (size_t)nb * nbb * 32));
+  KMG_TRY(c->gx_bits.ensure(sizeof(uint32_t) * (size_t)(na * nba + nb * nbb)));
+  uint32_t *bits_a = c->gx_bits.as<uint32_t>(), *bits_b = bits_a + na * nba;
+  const GkmxSide A{c->kmers.as<uint32_t>(), bits_a, na, nba};
+  const GkmxSide B{c->gx_words_b.as<uint32_t>(), bits_b, nb, nbb};
+  struct Side {
+    const uint8_t *codes; const int32_t *lens; int64_t n, ldc; int pmax; uint32_t *words, *bits;
+  } sides[2] = {{d_ca, d_la, na, ldc_a, pa, c->kmers.as<uint32_t>(), bits_a},
+                {d_cb, d_lb, nb, ldc_b, pb, c->gx_words_b.as<uint32_t>(), bits_b}};
+  for (const Side &q : sides) {  // one record buffer: the stream orders B's pack behind A's extract
+    const Packed pk{c->packed.as<uint32_t>(), (int64_t)(packed_cw(q.ldc) + packed_mw(q.ldc)),
+                    packed_cw(q.ldc)};
+    {
+      StageTimer t(c, ST_PACK);
+      KMG_HIP(launch_pack(q.codes, q.lens, q.n, q.ldc, 0, c->packed.as<uint32_t>(), c->stream));
+    }
+    StageTimer t(c, ST_EXTRACT);
+    KMG_HIP(launch_gkmx_extract(pk, q.n, l, q.pmax, q.words, q.bits, c->stream));
+  }
+  OutSpec o{d_out, ld, dt, 0, nullptr, nullptr};
+  const double *sa = nullptr, *sb = nullptr;
+  if (p->normalize) {  // sa in diagv, sb in dsq
+    KMG_TRY(c->diagv.ensure(sizeof(double) * (size_t)na));
+    KMG_TRY(c->dsq.ensure(sizeof(double) * (size_t)nb));
+    StageTimer t(c, ST_DIAG);
+    KMG_HIP(launch_gkmx_diag(A, l, wt, c->diagv.as<double>(), c->stream));
+    KMG_HIP(launch_gkmx_diag(B, l, wt, c->dsq.as<double>(), c->stream));
+    o.normalize = 1;
+    sa = c->diagv.as<double>();
+    sb = c->dsq.as<double>();
+  }
+  StageTimer t(c, ST_GKMX);
+  KMG_HIP(launch_gram_gkmx(A, B, l, wt, o, sa, sb, c->stream));
+  return KMG_OK;
+}
+
+int kmg_gkm_cross_device(kmg_ctx *c, const kmg_params *p, const uint8_t *d_codes_a,
+                         const int32_t *d_lens_a, int64_t na, int64_t ldc_a,
+                         const uint8_t *d_codes_b, const int32_t *d_lens_b, int64_t nb,
+                         int64_t ldc_b, int32_t out_dtype, void *d_out, int64_t ld_out) {
+  if (!c) return fail(KMG_EINVAL, "ctx is NULL");
+  std::lock_guard<std::mutex> lk(c->mu);
+  GkmWeights wt{};
+  KMG_TRY(gkm_cross_check(p, na, ldc_a, nb, ldc_b, out_dtype, wt));
+  // (device rows: the lengths are device data, so ldc bounds them, as in kmg_gram_device)
+  KMG_TRY(gkm_cross_bounds(p, wt, (int)ldc_a, na, (int)ldc_b, nb, out_dtype));
+  if (na == 0 || nb == 0) return KMG_OK;
+  if (!d_codes_a || !d_lens_a || !d_codes_b || !d_lens_b || !d_out)
+    return fail(KMG_EINVAL, "NULL buffer");
+  if (ld_out < nb) return fail(KMG_EINVAL, "ld_out < nb");
+  KMG_HIP(hipSetDevice(c->device));
+  return gkm_cross_device(c, p, wt, d_codes_a, d_lens_a, (int)ldc_a, na, ldc_a, d_codes_b, d_lens_b,
+                          (int)ldc_b, nb, ldc_b, out_dtype, d_out, ld_out);
+}
+
+int kmg_gkm_cross(kmg_ctx *c, const kmg_params *p, const uint8_t *codes_a, const int32_t *lens_a,
+                  int64_t na, int64_t ldc_a, const uint8_t *codes_b, const int32_t *lens_b,
+                  int64_t nb, int64_t ldc_b, int32_t out_dtype, void *out, int64_t ld_out) {
+  if (!c) return fail(KMG_EINVAL, "ctx is NULL");
+  std::lock_guard<std::mutex> lk(c->mu);
+  GkmWeights wt{};
+  KMG_TRY(gkm_cross_check(p, na, ldc_a, nb, ldc_b, out_dtype, wt));
+  const bool empty = na == 0 || nb == 0;
+  if (!empty && (!codes_a || !lens_a || !codes_b || !lens_b || !out))
+    return fail(KMG_EINVAL, "NULL buffer");
+  if (!empty && ld_out < nb) return fail(KMG_EINVAL, "ld_out < nb");
+  int maxlen[2] = {0, 0};
+  for (int s = 0; s < 2 && !empty; ++s) {
+    const int32_t *lens = s ? lens_b : lens_a;
+    const int64_t n = s ? nb : na, ldc = s ? ldc_b : ldc_a;
+    for (int64_t i = 0; i < n; ++i) {
+      if (lens[i] < 0 || lens[i] > ldc)
+        return fail(KMG_EINVAL, "lens_%c[%lld] outside [0,ldc]", s ? 'b' : 'a', (long long)i);
+      maxlen[s] = std::max(maxlen[s], (int)lens[i]);
+    }
+  }
+  KMG_TRY(gkm_cross_bounds(p, wt, maxlen[0], na, maxlen[1], nb, out_dtype));
+  if (empty) return KMG_OK;
+  KMG_HIP(hipSetDevice(c->device));
+  const size_t esz = dtype_size(out_dtype);
+  const int64_t ldd = (nb + 3) & ~3LL;
+  const size_t bytes_a = ((size_t)na * ldc_a + 15) & ~(size_t)15;
+  KMG_TRY(c->h_codes.ensure(bytes_a + (size_t)nb * ldc_b));
+  KMG_TRY(c->h_lens.ensure(sizeof(int32_t) * (size_t)(na + nb)));
+  KMG_TRY(c->h_out.ensure(esz * (size_t)na * ldd));
+  uint8_t *d_ca = c->h_codes.as<uint8_t>(), *d_cb = d_ca + bytes_a;
+  int32_t *d_la = c->h_lens.as<int32_t>(), *d_lb = d_la + na;
+  KMG_HIP(hipMemcpyAsync(d_ca, codes_a, (size_t)na * ldc_a, hipMemcpyHostToDevice, c->stream));
+  KMG_HIP(hipMemcpyAsync(d_cb, codes_b, (size_t)nb * ldc_b, hipMemcpyHostToDevice, c->stream));
+  KMG_HIP(hipMemcpyAsync(d_la, lens_a, sizeof(int32_t) * na, hipMemcpyHostToDevice, c->stream));
+  KMG_HIP(hipMemcpyAsync(d_lb, lens_b, sizeof(int32_t) * nb, hipMemcpyHostToDevice, c->stream));
+  KMG_TRY(gkm_cross_device(c, p, wt, d_ca, d_la, maxlen[0], na, ldc_a, d_cb, d_lb, maxlen[1], nb,
+                           ldc_b, out_dtype, c->h_out.p, ldd));
+  KMG_HIP(hipMemcpy2DAsync(out, (size_t)ld_out * esz, c->h_out.p, (size_t)ldd * esz,
+                           (size_t)nb * esz, (size_t)na, hipMemcpyDeviceToHost, c->stream));
+  KMG_HIP(hipStreamSynchronize(c->stream));
+  return KMG_OK;
 }
 
 int kmg_gram_device_cols(kmg_ctx *c, const kmg_params *p, const uint8_t *d_codes,

@@ -1,0 +1,357 @@
+// kmg_gkmx.hip — the rectangular gapped k-mer kernel for rows of any length, on int8 MFMA
+// (gfx950).
+//
+//   Kx[i][j] = sum_{a, b} h[ham(A_i[a:a+l], B_j[b:b+l])],  h[m] = C(l - m, k) for m <= d, else 0
+//
+// for two sequence sets A (na rows) and B (nb rows): the block K(queries x support vectors) of
+// gkm-SVM prediction, and with A = B the square Gram of rows past kmg_gkm.hip's 256 words.  The
+// word rules are KMG_GKM's (all windows of the whole row; a window holding a non-ACGT symbol
+// counts nothing), except that T^16 is a word like any other: validity is a bit beside the
+// word, not a marker value inside it.
+//
+// Word matches as a matrix product.  For 32 words of A_i and 32 words of B_j, one-hot operands
+// X[a][(p, c)] = [letter p of word a is c] give (X_A X_B^T)[a][b] = l - ham(a, b): 4 l <= 64
+// k-values, two v_mfma_i32_32x32x32_i8 steps (one at l <= 8).  Both operands hold 2 where the
+// letter is, so an accumulator entry is 4 * matches: the byte offset into the LDS table
+// hm[m] = h[l - m].  A word pair then costs one ds_read_b32 and one add.  hm[0] = h[l] = 0
+// (d <= l - k < l), so an all-zero operand -- an invalid word, a word past the row's end, a
+// letter position >= l -- counts nothing and needs no special case.
+//
+// gkmx_extract_kernel   packed records -> words [n][32 nblk] (0 where invalid) and validity
+//                       bits [n][nblk], nblk = ceil(pmax / 32) blocks of 32 words a row.
+// gram_gkmx_kernel<DIAG, TWO>   one 256-thread workgroup a tile of 16 rows x 8 columns.
+//   LDS     one chunk of 8 blocks (256 words) of every tile row and column, 4 B a word:
+//           16 KB + 8 KB, their validity words (768 B), hm (80 B) and the int64 result tile
+//           (1 KB): 26 KB whatever pmax is.  The chunk loops (A chunks outside, B chunks
+//           inside; the A chunk is staged once a sweep of the B chunks) are workgroup-uniform.
+//   waves   wave w owns the pairs (rows 4w .. 4w + 3) x (8 columns), whole.
+//   lanes   lane = (word slot 0..31, half).  A lane expands its word's 4 letters of each MFMA
+//           step into 4 dwords (16 k-values): step 0 takes letters 0..7 (half 0 letters 0..3,
+//           half 1 letters 4..7), step 1 letters 8..15 (TWO, l > 8).  The word is left-aligned
+//           first, so letter p sits at bits 31 - 2p, 30 - 2p for every l; the dword of a letter
+//           position >= l is built from the lane constant 0 instead of 2.  The same expansion
+//           serves both operands, so the lane / element -> k map is the same by construction.
+//   sweep   for each A block the four rows' operands are expanded once (32 VGPRs) and stay in
+//           registers while the wave walks the 8 columns' B blocks of the staged chunk: one
+//           ds_read_b32 and one expansion a B block, then per row 1 or 2 MFMAs and the 16
+//           lookups.  A B block whose 32 validity bits are all set skips the masking; one with
+//           none set, or an A block with none set in all four rows, is skipped (wave-uniform:
+//           the validity word is one LDS address a wave).
+//   sums    the 16 lookups of an MFMA result are added in int32 (<= 16 * 12870) and that sum
+//           goes into the pair's per-lane int64: an int32 never holds more than 16 adds.  One
+//           xor-shuffle reduction a pair at the end; the raw value is exact in int64 and is
+//           converted once to the output type.
+//   DIAG    pairs (i, i): a tile is 8 rows, staged on both sides; wave w owns rows 2w, 2w + 1
+//           and sweeps each against itself.  Writes sqrt(K_ii) (IEEE) for the normalisation.
+#include "kmg_internal.h"
+
+namespace kmg {
+
+namespace {
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int v16i __attribute__((ext_vector_type(16)));
+
+constexpr int GX_TR = 16;           // tile rows
+constexpr int GX_TC = 8;            // tile columns (and the rows of a DIAG tile)
+constexpr int GX_CB = 8;            // 32-word blocks a staged chunk
+constexpr int GX_CW = 32 * GX_CB;   // words a staged chunk
+
+// code and validity of window a of a packed record (pk_window with the validity kept apart)
+__device__ __forceinline__ uint32_t gx_window(const uint32_t *rec, int cw, int a, int l, bool &ok) {
+  const int i = a >> 4, sh = 2 * (a & 15);
+  const uint64_t v = ((uint64_t)rec[i] << 32) | rec[i + 1];
+  const int j = a >> 5;
+  const uint64_t m = ((((uint64_t)rec[cw + j + 1]) << 32) | rec[cw + j]) >> (a & 31);
+  ok = (m & ((1ull << l) - 1ull)) == 0;
+  return (uint32_t)((v << sh) >> (64 - 2 * l));
+}
+
+// one thread a word slot; a wave covers two 32-word blocks and writes their two validity words
+__global__ __launch_bounds__(256) void gkmx_extract_kernel(Packed pk, int64_t n, int l, int pmax,
+                                                           int nblk, uint32_t *__restrict__ words,
+                                                           uint32_t *__restrict__ bits) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t pp = (int64_t)nblk * 32;
+  const bool in = t < n * pp;
+  bool ok = false;
+  uint32_t code = 0;
+  if (in) {
+    const int64_t j = t / pp;
+    const int a = (int)(t - j * pp);
+    if (a < pmax) code = gx_window(pk.w + j * pk.ldp, pk.cw, a, l, ok);
+  }
+  const uint64_t b = __ballot(ok);
+  if (!in) return;
+  words[t] = ok ? code : 0u;
+  if ((threadIdx.x & 31) == 0) bits[t >> 5] = (uint32_t)(b >> (threadIdx.x & 32));
+}
+
+template <bool TWO>
+struct GxLane {
+  uint32_t val[TWO ? 8 : 4];  // 2 where the lane's letter position is < l, else 0
+  int lsh, sh0, sh1, lr;      // left-align shift, the two steps' letter-group shifts, word slot
+};
+
+// the lane's one-hot dwords of word w: x0 = MFMA step 0, x1 = step 1
+template <bool TWO>
+__device__ __forceinline__ void gx_expand(const GxLane<TWO> &L, uint32_t w, v4i &x0, v4i &x1) {
+  const uint32_t wl = w << L.lsh;
+  const uint32_t g0 = wl >> L.sh0;  // the group's 4 letters at bits 7..0 (bits above are masked)
+  x0[0] = (int)(L.val[0] << ((g0 >> 3) & 24u));
+  x0[1] = (int)(L.val[1] << ((g0 >> 1) & 24u));
+  x0[2] = (int)(L.val[2] << ((g0 << 1) & 24u));
+  x0[3] = (int)(L.val[3] << ((g0 << 3) & 24u));
+  if constexpr (TWO) {
+    const uint32_t g1 = wl >> L.sh1;
+    x1[0] = (int)(L.val[4] << ((g1 >> 3) & 24u));
+    x1[1] = (int)(L.val[5] << ((g1 >> 1) & 24u));
+    x1[2] = (int)(L.val[6] << ((g1 << 1) & 24u));
+    x1[3] = (int)(L.val[7] << ((g1 << 3) & 24u));
+  } else {
+    x1 = (v4i){};
+  }
+}
+
+template <bool TWO>
+__device__ __forceinline__ void gx_mask(const GxLane<TWO> &L, uint32_t vw, v4i &x0, v4i &x1) {
+  const int m = -(int)((vw >> L.lr) & 1u);
+  x0 &= m;
+  if constexpr (TWO) x1 &= m;
+}
+
+// NR rows' operands of one A block against the nbb staged blocks of one column
+template <int NR, bool TWO>
+__device__ __forceinline__ void gx_sweep(const GxLane<TWO> &L, const v4i (&a0)[NR],
+                                         const v4i (&a1)[NR], const uint32_t *wcol,
+                                         const uint32_t *vcol, int nbb, const int32_t *hm,
+                                         int64_t (&S)[NR]) {
+  for (int bb = 0; bb < nbb; ++bb) {
+    const uint32_t vw = __builtin_amdgcn_readfirstlane(vcol[bb]);
+    if (vw == 0u) continue;
+    v4i b0, b1;
+    gx_expand<TWO>(L, wcol[bb * 32 + L.lr], b0, b1);
+    if (vw != 0xFFFFFFFFu) gx_mask<TWO>(L, vw, b0, b1);
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      v16i acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0[r], b0, (v16i){}, 0, 0, 0);
+      if constexpr (TWO) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1[r], b1, acc, 0, 0, 0);
+      int t = 0;  // acc[e] = 4 * matches: the byte offset into hm
+#pragma unroll
+      for (int e = 0; e < 16; ++e) t += *(const int32_t *)((const char *)hm + acc[e]);
+      S[r] += t;
+    }
+  }
+}
+
+template <bool DIAG, bool TWO>
+__global__ __launch_bounds__(256) void gram_gkmx_kernel(GkmxSide A, GkmxSide B, int l, int64_t row0,
+                                                        int64_t rows, int64_t tiles_c,
+                                                        GkmWeights wt, OutSpec o,
+                                                        const double *__restrict__ sa,
+                                                        const double *__restrict__ sb,
+                                                        double *__restrict__ dsq_out) {
+  __shared__ __align__(16) uint32_t wa[GX_TR][GX_CW];
+  __shared__ __align__(16) uint32_t wb[GX_TC][GX_CW];
+  __shared__ uint32_t va[GX_TR][GX_CB], vb[GX_TC][GX_CB];
+  __shared__ int32_t hm[20];
+  __shared__ int64_t res[GX_TR][GX_TC];
+  constexpr int TRR = DIAG ? GX_TC : GX_TR;  // rows a tile
+  constexpr int NRW = DIAG ? 1 : 4;          // rows of one sweep
+  constexpr int NCW = DIAG ? 2 : GX_TC;      // sweeps' sums a wave
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int64_t i0, j0;
+  int nr, nc;
+  if constexpr (DIAG) {
+    i0 = j0 = (int64_t)blockIdx.x * GX_TC;
+    nr = nc = (int)min((int64_t)GX_TC, A.n - i0);
+  } else {
+    const int64_t tr = (int64_t)blockIdx.x / tiles_c, tc = (int64_t)blockIdx.x - tr * tiles_c;
+    i0 = row0 + tr * GX_TR;
+    j0 = tc * GX_TC;
+    nr = (int)min((int64_t)GX_TR, row0 + rows - i0);
+    nc = (int)min((int64_t)GX_TC, B.n - j0);
+  }
+
+  // hm[m] = h[l - m] (constant indices into wt only: it stays in scalar registers)
+#pragma unroll
+  for (int d = 0; d < 17; ++d)
+    if (tid == l - d) hm[tid] = wt.h[d];
+  if (tid > l && tid < 20) hm[tid] = 0;
+
+  GxLane<TWO> L;
+  L.lr = lane & 31;
+  const int half = lane >> 5;
+  L.lsh = 32 - 2 * l;
+  L.sh0 = 24 - 8 * half;
+  L.sh1 = 8 - 8 * half;
+#pragma unroll
+  for (int q = 0; q < (TWO ? 8 : 4); ++q) L.val[q] = (8 * (q >> 2) + 4 * half + (q & 3)) < l ? 2u : 0u;
+
+  int64_t S[NCW][NRW];
+#pragma unroll
+  for (int c = 0; c < NCW; ++c)
+#pragma unroll
+    for (int r = 0; r < NRW; ++r) S[c][r] = 0;
+
+  const int nca = (A.nblk + GX_CB - 1) / GX_CB, ncb = (B.nblk + GX_CB - 1) / GX_CB;
+  for (int ca = 0; ca < nca; ++ca) {
+    for (int cb = 0; cb < ncb; ++cb) {
+      __syncthreads();  // the previous chunk's sweeps are done (and hm is written)
+      if (cb == 0) {
+        for (int t = tid; t < TRR * (GX_CW / 4); t += 256) {
+          const int r = t / (GX_CW / 4), q4 = (t % (GX_CW / 4)) * 4, blk = ca * GX_CB + (q4 >> 5);
+          uint4 v = make_uint4(0u, 0u, 0u, 0u);
+          if (r < nr && blk < A.nblk)
+            v = *(const uint4 *)(A.words + ((i0 + r) * A.nblk + blk) * 32 + (q4 & 31));
+          *(uint4 *)&wa[r][q4] = v;
+        }
+        if (tid < TRR * GX_CB) {
+          const int r = tid / GX_CB, blk = ca * GX_CB + tid % GX_CB;
+          va[r][tid % GX_CB] = (r < nr && blk < A.nblk) ? A.bits[(i0 + r) * A.nblk + blk] : 0u;
+        }
+      }
+      for (int t = tid; t < GX_TC * (GX_CW / 4); t += 256) {
+        const int r = t / (GX_CW / 4), q4 = (t % (GX_CW / 4)) * 4, blk = cb * GX_CB + (q4 >> 5);
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (r < nc && blk < B.nblk)
+          v = *(const uint4 *)(B.words + ((j0 + r) * B.nblk + blk) * 32 + (q4 & 31));
+        *(uint4 *)&wb[r][q4] = v;
+      }
+      if (tid < GX_TC * GX_CB) {
+        const int r = tid / GX_CB, blk = cb * GX_CB + tid % GX_CB;
+        vb[r][tid % GX_CB] = (r < nc && blk < B.nblk) ? B.bits[(j0 + r) * B.nblk + blk] : 0u;
+      }
+      __syncthreads();
+
+      const int nba = min(GX_CB, A.nblk - ca * GX_CB), nbb = min(GX_CB, B.nblk - cb * GX_CB);
+      if constexpr (DIAG) {
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr) {
+          const int r = 2 * wave + rr;
+          if (r >= nr) continue;  // wave-uniform
+          for (int ab = 0; ab < nba; ++ab) {
+            const uint32_t vw = __builtin_amdgcn_readfirstlane(va[r][ab]);
+            if (vw == 0u) continue;
+            v4i a0[1], a1[1];
+            gx_expand<TWO>(L, wa[r][ab * 32 + L.lr], a0[0], a1[0]);
+            gx_mask<TWO>(L, vw, a0[0], a1[0]);
+            gx_sweep<1, TWO>(L, a0, a1, wb[r], vb[r], nbb, hm, S[rr]);
+          }
+        }
+      } else {
+        const int rb = 4 * wave;
+        if (rb < nr) {  // wave-uniform
+          for (int ab = 0; ab < nba; ++ab) {
+            v4i a0[4], a1[4];
+            uint32_t any = 0u;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const uint32_t vw = va[rb + r][ab];
+              any |= vw;
+              gx_expand<TWO>(L, wa[rb + r][ab * 32 + L.lr], a0[r], a1[r]);
+              gx_mask<TWO>(L, vw, a0[r], a1[r]);
+            }
+            if (__builtin_amdgcn_readfirstlane(any) == 0u) continue;
+#pragma unroll
+            for (int c = 0; c < GX_TC; ++c)
+              if (c < nc) gx_sweep<4, TWO>(L, a0, a1, wb[c], vb[c], nbb, hm, S[c]);
+          }
+        }
+      }
+    }
+  }
+
+  // one cross-lane reduction a pair
+#pragma unroll
+  for (int c = 0; c < NCW; ++c)
+#pragma unroll
+    for (int r = 0; r < NRW; ++r) {
+      int64_t v = S[c][r];
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+      if (lane == 0) {
+        if constexpr (DIAG) res[2 * wave + c][0] = v;
+        else res[4 * wave + r][c] = v;
+      }
+    }
+  __syncthreads();
+
+  if constexpr (DIAG) {
+    if (tid < nr) dsq_out[i0 + tid] = __builtin_sqrt((double)res[tid][0]);  // IEEE sqrt
+  } else {
+    const int r = tid / GX_TC, c = tid % GX_TC;
+    if (tid < GX_TR * GX_TC && r < nr && c < nc) {
+      const int64_t v = res[r][c];
+      const int64_t at = (i0 - row0 + r) * o.ld + j0 + c;
+      if (o.dtype == KMG_I32) {
+        ((int32_t *)o.out)[at] = (int32_t)v;
+      } else {
+        const double x = o.normalize ? (double)v / (sa[i0 + r] * sb[j0 + c]) : (double)v;
+        if (o.dtype == KMG_F64) ((double *)o.out)[at] = x;
+        else ((float *)o.out)[at] = (float)x;
+      }
+    }
+  }
+}
+
+}  // namespace
+
+hipError_t launch_gkmx_extract(const Packed &pk, int64_t n, int l, int pmax, uint32_t *words,
+                               uint32_t *bits, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (pmax < 1 || l < 1 || l > 16) return hipErrorInvalidValue;
+  const int nblk = gkmx_blocks(pmax);
+  const int64_t blocks = (n * nblk * 32 + 255) / 256;
+  if (blocks >= KMG_GKM_MAX_TILES) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gkmx_extract_kernel, dim3((unsigned)blocks), dim3(256), 0, s, pk, n, l, pmax,
+                     nblk, words, bits);
+  return hipGetLastError();
+}
+
+hipError_t launch_gram_gkmx(const GkmxSide &A, const GkmxSide &B, int l, const GkmWeights &wt,
+                            const OutSpec &o, const double *sa, const double *sb, hipStream_t s) {
+  if (A.n <= 0 || B.n <= 0) return hipSuccess;
+  if (l < 1 || l > 16 || A.nblk < 1 || B.nblk < 1) return hipErrorInvalidValue;
+  if (o.normalize && (!sa || !sb)) return hipErrorInvalidValue;
+  const int64_t tiles_c = (B.n + GX_TC - 1) / GX_TC;
+  if (tiles_c >= KMG_GKM_MAX_TILES) return hipErrorInvalidValue;  // AQL grid size is 32-bit
+  const int64_t max_rows = (KMG_GKM_MAX_TILES - 1) / tiles_c * GX_TR;
+  const size_t esz = o.dtype == KMG_F64 ? 8 : 4;
+  for (int64_t r0 = 0; r0 < A.n; r0 += max_rows) {
+    const int64_t rows = A.n - r0 < max_rows ? A.n - r0 : max_rows;
+    const dim3 grid((unsigned)((rows + GX_TR - 1) / GX_TR * tiles_c));
+    OutSpec os = o;
+    os.out = (char *)o.out + (size_t)r0 * o.ld * esz;
+    if (l > 8)
+      hipLaunchKernelGGL((gram_gkmx_kernel<false, true>), grid, dim3(256), 0, s, A, B, l, r0, rows,
+                         tiles_c, wt, os, sa, sb, (double *)nullptr);
+    else
+      hipLaunchKernelGGL((gram_gkmx_kernel<false, false>), grid, dim3(256), 0, s, A, B, l, r0, rows,
+                         tiles_c, wt, os, sa, sb, (double *)nullptr);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_gkmx_diag(const GkmxSide &A, int l, const GkmWeights &wt, double *dsq,
+                            hipStream_t s) {
+  if (A.n <= 0) return hipSuccess;
+  if (l < 1 || l > 16 || A.nblk < 1) return hipErrorInvalidValue;
+  const int64_t tiles = (A.n + GX_TC - 1) / GX_TC;
+  if (tiles >= KMG_GKM_MAX_TILES) return hipErrorInvalidValue;
+  const OutSpec o{};
+  if (l > 8)
+    hipLaunchKernelGGL((gram_gkmx_kernel<true, true>), dim3((unsigned)tiles), dim3(256), 0, s, A, A,
+                       l, (int64_t)0, A.n, (int64_t)1, wt, o, (const double *)nullptr,
+                       (const double *)nullptr, dsq);
+  else
+    hipLaunchKernelGGL((gram_gkmx_kernel<true, false>), dim3((unsigned)tiles), dim3(256), 0, s, A, A,
+                       l, (int64_t)0, A.n, (int64_t)1, wt, o, (const double *)nullptr,
+                       (const double *)nullptr, dsq);
+  return hipGetLastError();
+}
+
+}  // namespace kmg

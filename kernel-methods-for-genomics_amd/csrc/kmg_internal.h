@@ -295,6 +295,27 @@ hipError_t launch_gram_gkm(const uint32_t *words, int pmax, int l, int64_t n, in
 hipError_t launch_gkm_diag(const uint32_t *words, int pmax, int l, int64_t n, const GkmWeights &wt,
                            double *diagv, double *dsq, hipStream_t s);
 
+// ---------------------------------------------------------------- gkm cross (kmg_gkmx.hip)
+// rectangular gkm block Kx[i][j] = sum_{a,b} h[ham(A_i word a, B_j word b)] on int8 MFMA, rows
+// of any length.  One side's words: [n][32 nblk] uint32 (0 where invalid) and validity bits
+// [n][nblk] (bit t of word q: word 32 q + t counts), nblk = gkmx_blocks(pmax)
+struct GkmxSide {
+  const uint32_t *words;
+  const uint32_t *bits;
+  int64_t n;
+  int nblk;
+};
+inline int gkmx_blocks(int pmax) { return (pmax + 31) / 32; }
+hipError_t launch_gkmx_extract(const Packed &pk, int64_t n, int l, int pmax, uint32_t *words,
+                               uint32_t *bits, hipStream_t s);
+// all A.n x B.n pairs at o.out (o.out, o.ld, o.dtype, o.normalize are read); normalised:
+// raw / (sa[i] * sb[j]).  Rows are split so every launch stays below KMG_GKM_MAX_TILES tiles.
+hipError_t launch_gram_gkmx(const GkmxSide &A, const GkmxSide &B, int l, const GkmWeights &wt,
+                            const OutSpec &o, const double *sa, const double *sb, hipStream_t s);
+// dsq[i] = sqrt(K(A_i, A_i)), from the same kernel over the pairs (i, i)
+hipError_t launch_gkmx_diag(const GkmxSide &A, int l, const GkmWeights &wt, double *dsq,
+                            hipStream_t s);
+
 // ---------------------------------------------------------------- scorer (kmg_score.hip)
 // V[key] = sum over the key's posting lists (exact index, copies = 1, every chunk) of the
 // 128-bit fixed-point weights fix[2 row], fix[2 row + 1] (low, high word), rounded once to

@@ -21,7 +21,8 @@ from kmgram.params import beta, delta  # noqa: F401  (reference helpers, kernels
 
 __all__ = [
     "get_spectrum_K", "get_WD_K", "get_WDShifts_K", "get_mismatch_K", "get_LA_K",
-    "get_string_K", "get_gappy_K", "get_gkm_K", "center_K", "normalize_K", "select_method",
+    "get_string_K", "get_gappy_K", "get_gkm_K", "get_gkm_cross_K", "center_K", "normalize_K",
+    "select_method",
     "beta", "delta", "letter_to_num", "format", "S", "get_WD_d", "get_WDShifts_d", "K_k",
     "affine_align", "Smith_Waterman", "get_phi_u", "get_phi_km", "gappy_k", "B_k", "rec",
 ]
@@ -75,6 +76,14 @@ def get_gkm_K(X, l, k, d=None):
     d=None is min(3, l - k)), normalised.  Not in the reference: ``select_method`` has no
     method string for it."""
     return _eng().gkm(_seqs(X), l, k, d)
+
+
+def get_gkm_cross_K(Xa, Xb, l, k, d=None):
+    """Gapped k-mer block K(Xa rows, Xb rows), normalised by both sides' own diagonals: the
+    K(queries, support vectors) of gkm-SVM prediction, rows of any length.
+    ``get_gkm_cross_K(X, X, ...)`` is the square gkm Gram of rows too long for ``get_gkm_K``
+    (its diagonal is K_ii / (s_i s_i), 1 up to one rounding, not filled in)."""
+    return _eng().gkm_cross(_seqs(Xa), _seqs(Xb), l, k, d)
 
 
 # ----------------------------------------------------------------------- helpers

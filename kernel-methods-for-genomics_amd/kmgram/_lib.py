@@ -39,6 +39,7 @@ EXPORTS = (
     "kmg_gram_to_host", "kmg_gram_blocks_wire", "kmg_last_plan", "kmg_features",
     "kmg_last_factorisation", "kmg_features_sym", "kmg_gram_device_cols",
     "kmg_scorer_create", "kmg_scorer_score", "kmg_scorer_score_device", "kmg_scorer_destroy",
+    "kmg_gkm_cross", "kmg_gkm_cross_device",
 )
 KMG_FEATURES_BCAST = 1
 KMG_FACTOR_CHOLESKY, KMG_FACTOR_LU_ASYMMETRIC, KMG_FACTOR_LU_INDEFINITE = 1, 2, 3
@@ -97,6 +98,10 @@ def load():
                                  I64], ctypes.c_int),
             "kmg_gram_device_cols": ([P, ctypes.POINTER(KmgParams), P, P, I64, I64, I64, I64, I32,
                                       P, I64], ctypes.c_int),
+            "kmg_gkm_cross": ([P, ctypes.POINTER(KmgParams), P, P, I64, I64, P, P, I64, I64, I32,
+                               P, I64], ctypes.c_int),
+            "kmg_gkm_cross_device": ([P, ctypes.POINTER(KmgParams), P, P, I64, I64, P, P, I64, I64,
+                                      I32, P, I64], ctypes.c_int),
             "kmg_features": ([P, ctypes.POINTER(KmgParams), P, P, I64, I64, P, I64, P, I64],
                              ctypes.c_int),
             "kmg_features_sym": ([P, ctypes.POINTER(KmgParams), P, P, I64, I64, P, I64, I32, P,
@@ -248,6 +253,27 @@ class Context:
         check(self.lib.kmg_gram(self._h, ctypes.byref(params), ptr(codes), ptr(lens), n, ldc,
                                 out_dtype, ptr(out), n))
         return out
+
+    def gkm_cross(self, params, codes_a, lens_a, codes_b, lens_b, out_dtype=KMG_F64):
+        """[na, nb] gapped k-mer block between the rows of A and of B, rows of any length
+        (kmg_gkm_cross; params from ``params.gkm``)."""
+        codes_a = np.ascontiguousarray(codes_a, dtype=np.uint8)
+        codes_b = np.ascontiguousarray(codes_b, dtype=np.uint8)
+        lens_a = np.ascontiguousarray(lens_a, dtype=np.int32)
+        lens_b = np.ascontiguousarray(lens_b, dtype=np.int32)
+        (na, ldc_a), (nb, ldc_b) = codes_a.shape, codes_b.shape
+        out = np.empty((na, nb), dtype=DTYPES[out_dtype])
+        check(self.lib.kmg_gkm_cross(self._h, ctypes.byref(params), ptr(codes_a), ptr(lens_a), na,
+                                     ldc_a, ptr(codes_b), ptr(lens_b), nb, ldc_b, out_dtype,
+                                     ptr(out), nb))
+        return out
+
+    def gkm_cross_device(self, params, d_codes_a, d_lens_a, na, ldc_a, d_codes_b, d_lens_b, nb,
+                         ldc_b, out_dtype, d_out, ld):
+        """The same on device pointers, on the context stream, without synchronising."""
+        check(self.lib.kmg_gkm_cross_device(self._h, ctypes.byref(params), d_codes_a, d_lens_a, na,
+                                            ldc_a, d_codes_b, d_lens_b, nb, ldc_b, out_dtype,
+                                            d_out, ld))
 
     def features(self, params, codes, lens, cols):
         """float64 [n, len(cols)] feature rows (kmg_features): column j scores the k-mer code

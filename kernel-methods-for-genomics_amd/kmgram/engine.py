@@ -197,6 +197,31 @@ class GramEngine:
                                      "its diagonal would be 0 under normalize=True")
         return self._run(p, seqs, out_dtype)
 
+    def gkm_cross(self, seqs_a, seqs_b, l, k, d=None, normalize=True, out_dtype=L.KMG_F64):
+        """Rectangular gapped k-mer block [len(seqs_a), len(seqs_b)]:
+        K_ij = sum_{a,b} h[ham(A_i[a:a+l], B_j[b:b+l])] with ``gkm``'s h and word rules, rows
+        of any length, T^16 counted (kmg_gkm_cross: int8 MFMA).  This is K(queries, support
+        vectors) for prediction; ``gkm_cross(s, s)`` is the way to a square gkm Gram of rows
+        longer than ``gkm`` takes.  normalize=True divides by sqrt(K(A_i, A_i) K(B_j, B_j)),
+        and a row without a valid word on either side raises ValueError."""
+        p = P.gkm(l, k, d, normalize)
+        seqs_a, seqs_b = list(seqs_a), list(seqs_b)
+        if normalize:
+            if out_dtype == L.KMG_I32:
+                raise ValueError("gkm: normalised output needs a floating dtype")
+            word = re.compile("[ACGT]{%d}" % int(l))
+            for side, seqs in (("a", seqs_a), ("b", seqs_b)):
+                for i, s in enumerate(seqs):
+                    if not word.search(s):
+                        raise ValueError(f"gkm: sequence {i} of side {side} has no all-ACGT word "
+                                         f"of length {int(l)}; its diagonal would be 0 under "
+                                         "normalize=True")
+        if not seqs_a or not seqs_b:
+            return np.zeros((len(seqs_a), len(seqs_b)), dtype=L.DTYPES[out_dtype])
+        codes_a, lens_a = E.encode(seqs_a)
+        codes_b, lens_b = E.encode(seqs_b)
+        return self.ctx.gkm_cross(p, codes_a, lens_a, codes_b, lens_b, out_dtype)
+
     # ------------------------------------------------------------------ scoring
     def scorer(self, method, seqs, coef):
         """Scorer of f(q) = sum_t coef[t] K(q, seqs[t]) + bias for K = select_method(., method),

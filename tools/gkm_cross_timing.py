@@ -1,0 +1,130 @@
+#!/usr/bin/env python3
+"""Times the rectangular gkm kernel against the square path's row-range form on
+the same seeded sequences (L = 101, l = 10, k = 6, d = 3, raw int32):
+
+  cross  kmg_gkm_cross_device, rows [0, N/2) x rows [N/2, N)       (gram_gkmx_kernel, int8 MFMA)
+  rows   kmg_gram_device, KMG_GKM, rows [0, N/2) x all N columns   (gram_gkm_kernel, not SYM);
+         twice the pairs, so its time is halved for the comparison
+
+Both alternate in one process after a warm-up of each; the kernel stage of every call is timed
+by the library's device events.  A sample of the cross result is checked against the formula at
+the timed sizes.  One point has no yardstick: 256 rows of 1000 letters against themselves,
+reported as word pairs a second.  One JSON file.
+"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "kernel-methods-for-genomics_amd"))
+
+from kmgram import _lib as L  # noqa: E402
+from kmgram import encode as E  # noqa: E402
+from kmgram import params as P  # noqa: E402
+
+LW, KI, D = 10, 6, 3
+
+
+def formula(ca, cb):
+    h = np.array(P.gkm_weights(LW, KI, D), dtype=np.int64)
+    w = np.lib.stride_tricks.sliding_window_view
+    return int(h[(w(ca, LW)[:, None, :] != w(cb, LW)[None, :, :]).sum(-1)].sum())
+
+
+def at(d, off):
+    return ctypes.c_void_p(d.value + int(off))
+
+
+def sampled_wrong(ctx, d_K, codes_a, codes_b, rng, count=32):
+    na, nb = len(codes_a), len(codes_b)
+    pairs = [(0, 0), (na - 1, nb - 1), (0, nb - 1), (na - 1, 0)] + \
+            [(int(rng.integers(0, na)), int(rng.integers(0, nb))) for _ in range(count - 4)]
+    row = np.empty(nb, dtype=np.int32)
+    bad = 0
+    for i, j in pairs:
+        ctx.d2h(row, at(d_K, 4 * i * nb))
+        bad += int(row[j]) != formula(codes_a[i], codes_b[j])
+    return bad, len(pairs)
+
+
+def run(ctx, n, reps, rng):
+    codes, lens = E.synthetic(n, 101, seed=5)
+    ldc, h = codes.shape[1], n // 2
+    d_codes, d_lens, d_K = ctx.dmalloc(codes.nbytes), ctx.dmalloc(lens.nbytes), ctx.dmalloc(4 * h * n)
+    ctx.h2d(d_codes, codes)
+    ctx.h2d(d_lens, lens)
+    p = P.gkm(LW, KI, D, normalize=False)
+    ctx.set_timing(True)
+    dev = {"cross": [], "rows": []}
+    for rep in range(reps + 1):  # one warm-up round of both routes
+        ctx.gram_device(p, d_codes, d_lens, n, ldc, 0, h, L.KMG_I32, d_K, n)
+        ctx.synchronize()
+        if rep >= 1:
+            dev["rows"].append(ctx.stage_ms("gkm"))
+        ctx.gkm_cross_device(p, d_codes, d_lens, h, ldc, at(d_codes, h * ldc), at(d_lens, 4 * h),
+                             n - h, ldc, L.KMG_I32, d_K, n - h)
+        ctx.synchronize()
+        if rep >= 1:
+            dev["cross"].append(ctx.stage_ms("gkmx"))
+    bad, cnt = sampled_wrong(ctx, d_K, codes[:h], codes[h:], rng)
+    for d in (d_codes, d_lens, d_K):
+        ctx.dfree(d)
+    pw = 101 - LW + 1
+    pairs = h * (n - h) * pw * pw  # word pairs of the cross block
+    med = {r: float(np.median(v)) for r, v in dev.items()}
+    same = {"cross": med["cross"], "rows": med["rows"] * (n - h) / n}  # ms at the cross block's pairs
+    return {"n": n, "reps": reps, "words_a_row": pw, "stage_ms_median": med, "stage_ms_all": dev,
+            "ms_at_equal_pairs": same, "ratio_rows_over_cross": same["rows"] / same["cross"],
+            "word_pairs": pairs, "word_pairs_per_s": {r: pairs / (same[r] * 1e-3) for r in same},
+            "sampled_entries_wrong": bad, "sampled_entries": cnt}
+
+
+def run_long(ctx, n, length, reps, rng):
+    codes, lens = E.synthetic(n, length, seed=6)
+    ldc = codes.shape[1]
+    d_codes, d_lens, d_K = ctx.dmalloc(codes.nbytes), ctx.dmalloc(lens.nbytes), ctx.dmalloc(4 * n * n)
+    ctx.h2d(d_codes, codes)
+    ctx.h2d(d_lens, lens)
+    p = P.gkm(LW, KI, D, normalize=False)
+    ctx.set_timing(True)
+    ms = []
+    for rep in range(reps + 1):
+        ctx.gkm_cross_device(p, d_codes, d_lens, n, ldc, d_codes, d_lens, n, ldc, L.KMG_I32, d_K, n)
+        ctx.synchronize()
+        if rep >= 1:
+            ms.append(ctx.stage_ms("gkmx"))
+    bad, cnt = sampled_wrong(ctx, d_K, codes[:, :length], codes[:, :length], rng, 8)
+    for d in (d_codes, d_lens, d_K):
+        ctx.dfree(d)
+    pw = length - LW + 1
+    med = float(np.median(ms))
+    return {"n": n, "length": length, "reps": reps, "words_a_row": pw, "stage_ms_median": med,
+            "stage_ms_all": ms, "word_pairs": n * n * pw * pw,
+            "word_pairs_per_s": n * n * pw * pw / (med * 1e-3),
+            "sampled_entries_wrong": bad, "sampled_entries": cnt}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gkm_cross_timing.json"))
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--sizes", default="2000,9000")
+    ap.add_argument("--long", default="256x1000")
+    a = ap.parse_args()
+    ctx = L.Context(0)
+    rng = np.random.default_rng(12)
+    res = [run(ctx, int(n), a.reps, rng) for n in a.sizes.split(",")]
+    ln, ll = (int(v) for v in a.long.split("x"))
+    long_res = run_long(ctx, ln, ll, a.reps, rng)
+    ctx.close()
+    with open(a.out, "w") as f:
+        json.dump({"l": LW, "k": KI, "d": D, "sizes": res, "long_rows": long_res}, f, indent=1)
+    print(json.dumps([{k: v for k, v in r.items() if k != "stage_ms_all"} for r in res + [long_res]]))
+
+
+if __name__ == "__main__":
+    main()
