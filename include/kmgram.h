@@ -72,7 +72,19 @@ enum {
                          kmg_gram_blocks, kmg_scorer_create and kmg_features* return
                          KMG_EUNSUPPORTED.  At l = 16 the word T^16 shares the 32 bits of the
                          invalid-word marker and is not counted.  kmg_gkm_cross* lift both
-                         limits (rows of any length, T^16 counted) for rectangular blocks. */
+                         limits (rows of any length, T^16 counted) for rectangular blocks.
+                         kmg_params.strands = 2 counts both strands, gkm-SVM's default:
+                           K2(x, y) = K(x, y) + K(x, rc(y))
+                         rc(y) the reverse complement of y (letters reversed, A<->T, C<->G; a
+                         word holding another symbol is invalid on both strands).  K2 is
+                         symmetric and is half the inner product of the strand-symmetrised
+                         feature map c(x) + c(rc(x)); the factor 2 cancels under normalisation,
+                         whose diagonals K2(x, x) carry their own reverse-complement term.
+                         strands = 0 or 1 is the single strand as read; any other value is
+                         KMG_EINVAL.  Raw values stay exact integers < 2^31 (2 * 256^2 C(16, 8)).
+                         With strands = 2 the Gram entry points refuse l = 16 with
+                         KMG_EUNSUPPORTED (rc(A^16) = T^16 would meet the invalid-word marker on
+                         one strand only); kmg_gkm_cross* serve it. */
 };
 
 /* output element types */
@@ -106,7 +118,9 @@ typedef struct kmg_params {
   int32_t la_mode;   /* LA: KMG_LA_REFERENCE / KMG_LA_INTENDED; GP: KMG_MODE_* */
   int32_t span;      /* WD/WDS: summation length L of get_WD_d / get_WDShifts_d (kernels.py:64,
                         115); 0 = len(x) of the smaller-index row, as get_*_K pass it */
-  int32_t reserved[5];
+  int32_t strands;   /* GKM: 0 or 1 = the strand as read, 2 = both strands (K + K(., rc(.)));
+                        every other family: 2 is KMG_EUNSUPPORTED before any allocation */
+  int32_t reserved[4];
   double lambda;     /* SS lambda */
   double lambda2;    /* SS lambda**2 exactly as the host language computes it */
   double la_e, la_d, la_beta; /* LA gap open / extend / beta */
@@ -155,6 +169,9 @@ int kmg_gram_device(kmg_ctx *ctx, const kmg_params *p, const uint8_t *d_codes,
  * With P_a, P_b the word counts of the longest rows: P_a P_b h[0] >= 2^53 is KMG_EUNSUPPORTED;
  * KMG_I32 with P_a P_b h[0] >= 2^31, or with normalize = 1, is KMG_EINVAL; na = 0 or nb = 0
  * returns KMG_OK and writes nothing.  All of it is checked before any allocation or launch.
+ * p->strands = 2: out[i][j] = K(A_i, B_j) + K(A_i, rc(B_j)) (KMG_GKM above), the reverse
+ * complement made in registers from the same staged words; every bound above then counts both
+ * strands (2 P_a P_b h[0]), the normalising diagonals too, and l = 16 is served.
  * Host buffers in and out, synchronous.
  */
 int kmg_gkm_cross(kmg_ctx *ctx, const kmg_params *p, const uint8_t *codes_a, const int32_t *lens_a,

@@ -351,6 +351,8 @@ int gkm_check(const kmg_params *p, int32_t dt, GkmWeights &wt) {
   if (d < 0 || d > gap) return fail(KMG_EINVAL, "gkm: truncation m = %d outside 0..g (g = %d)", d, gap);
   if (dt == KMG_I32 && p->normalize)
     return fail(KMG_EINVAL, "normalised output needs a floating dtype");
+  if (p->strands < 0 || p->strands > 2)
+    return fail(KMG_EINVAL, "gkm: strands = %d (0 or 1: as read, 2: both strands)", p->strands);
   int64_t binom[17][17] = {};
   for (int a = 0; a <= 16; ++a) {
     binom[a][0] = 1;
@@ -361,13 +363,21 @@ int gkm_check(const kmg_params *p, int32_t dt, GkmWeights &wt) {
   return KMG_OK;
 }
 
+// both strands (kmg_params.strands = 2) is the gkm kernel's only
+int strands_check(const kmg_params *p) {
+  if (p->kind != KMG_GKM && p->strands == 2)
+    return fail(KMG_EUNSUPPORTED, "strands = 2 (both strands) is served for KMG_GKM only (kind %d)",
+                p->kind);
+  return KMG_OK;
+}
+
 int check_params(const kmg_params *p, int64_t n, int64_t ldc, int32_t dt) {
   if (!p) return fail(KMG_EINVAL, "params is NULL");
   if (n < 0) return fail(KMG_EINVAL, "n < 0");
   if (ldc <= 0 && n > 0) return fail(KMG_EINVAL, "ldc must be > 0");
   if (dt != KMG_I32 && dt != KMG_F32 && dt != KMG_F64)
     return fail(KMG_EINVAL, "unknown out dtype %d", dt);
-  return KMG_OK;
+  return strands_check(p);
 }
 
 // ----------------------------------------------------------------- posting index
@@ -1524,6 +1534,10 @@ int gram_device(kmg_ctx *c, const kmg_params *p, const uint8_t *d_codes, const i
       const int l = p->k;
       GkmWeights wt{};
       KMG_TRY(gkm_check(p, dt, wt));
+      const bool rc = p->strands == 2;
+      if (rc && l == 16)
+        return fail(KMG_EUNSUPPORTED, "gkm: both strands at l = 16 is not served here (rc(A^16) = "
+                    "T^16 is the invalid-word marker); use kmg_gkm_cross");
       IndexGeom g{};
       g.k = l;
       g.n = n;
@@ -1552,7 +1566,7 @@ int gram_device(kmg_ctx *c, const kmg_params *p, const uint8_t *d_codes, const i
         KMG_TRY(c->diagv.ensure(sizeof(double) * (size_t)(n > 0 ? n : 1)));
         KMG_TRY(c->dsq.ensure(sizeof(double) * (size_t)(n > 0 ? n : 1)));
         StageTimer t(c, ST_DIAG);
-        KMG_HIP(launch_gkm_diag(c->kmers.as<uint32_t>(), g.pmax, l, n, wt, c->diagv.as<double>(),
+        KMG_HIP(launch_gkm_diag(c->kmers.as<uint32_t>(), g.pmax, l, rc, n, wt, c->diagv.as<double>(),
                                 c->dsq.as<double>(), c->stream));
         o.normalize = 1;
         o.diagv = c->diagv.as<double>();
@@ -1569,11 +1583,11 @@ int gram_device(kmg_ctx *c, const kmg_params *p, const uint8_t *d_codes, const i
       return each_range(c, ranges, o, after, [&](int64_t r0, int64_t r1, const OutSpec &oq) {
         StageTimer t(c, ST_GKM);
         if (sym)
-          return launch_gram_gkm(c->kmers.as<uint32_t>(), g.pmax, l, n, r0, r1, true, wt, oq, c->stream);
+          return launch_gram_gkm(c->kmers.as<uint32_t>(), g.pmax, l, rc, n, r0, r1, true, wt, oq, c->stream);
         for (int64_t r = r0; r < r1; r += max_rows) {
           OutSpec os = oq;
           os.out = (char *)oq.out + (size_t)(r - r0) * oq.ld * dtype_size(dt);
-          hipError_t e = launch_gram_gkm(c->kmers.as<uint32_t>(), g.pmax, l, n, r, std::min(r1, r + max_rows),
+          hipError_t e = launch_gram_gkm(c->kmers.as<uint32_t>(), g.pmax, l, rc, n, r, std::min(r1, r + max_rows),
                                          false, wt, os, c->stream);
           if (e != hipSuccess) return e;
         }
@@ -1715,6 +1729,7 @@ static int features_impl(kmg_ctx *c, const kmg_params *p, const uint8_t *codes, 
   if (n == 0 || ncols == 0) return KMG_OK;
   if (!codes || !lens || !cols || !out) return fail(KMG_EINVAL, "NULL buffer");
   if (ld_out < ncols) return fail(KMG_EINVAL, "ld_out < ncols");
+  KMG_TRY(strands_check(p));
   int k = p->k, m = 0, window = 0, binary = 0;
   const int bcast = sym && (flags & KMG_FEATURES_BCAST) ? 1 : 0;
   switch (p->kind) {
@@ -1829,14 +1844,17 @@ static int gkm_cross_bounds(const kmg_params *p, const GkmWeights &wt, int maxle
   const int l = p->k;
   const int pa = std::max(1, maxlen_a - l + 1), pb = std::max(1, maxlen_b - l + 1);
   const double two53 = 9007199254740992.0, h0 = (double)wt.h[0];
-  // every raw value is an exact integer in float64 (and in int32 where that is the output)
-  const double top = (double)pa * (double)pb * h0;
-  const double dtop = (double)std::max(pa, pb) * (double)std::max(pa, pb) * h0;
+  // every raw value is an exact integer in float64 (and in int32 where that is the output);
+  // both strands count twice the pairs, in the block and in the diagonals
+  const double ns = p->strands == 2 ? 2.0 : 1.0;
+  const double top = ns * (double)pa * (double)pb * h0;
+  const double dtop = ns * (double)std::max(pa, pb) * (double)std::max(pa, pb) * h0;
   if (top >= two53 || (p->normalize && dtop >= two53))
-    return fail(KMG_EUNSUPPORTED, "gkm cross: %d x %d words a pair can reach 2^53", pa, pb);
+    return fail(KMG_EUNSUPPORTED, "gkm cross: %d x %d words a pair (%d strand%s) can reach 2^53", pa,
+                pb, (int)ns, ns > 1 ? "s" : "");
   if (dt == KMG_I32 && top >= 2147483648.0)
-    return fail(KMG_EINVAL, "gkm cross: %d x %d words a pair can pass int32; use a floating dtype",
-                pa, pb);
+    return fail(KMG_EINVAL, "gkm cross: %d x %d words a pair (%d strand%s) can pass int32; use a "
+                "floating dtype", pa, pb, (int)ns, ns > 1 ? "s" : "");
   const int nba = gkmx_blocks(pa), nbb = gkmx_blocks(pb);
   const int64_t limit = KMG_GKM_MAX_TILES * 8;  // rows a launch grid reaches, words an extract
   if (na >= limit || nb >= limit || (double)na * nba * 32 >= (double)limit * 32 ||
@@ -1855,6 +1873,7 @@ static int gkm_cross_device(kmg_ctx *c, const kmg_params *p, const GkmWeights &w
                             int64_t nb, int64_t ldc_b, int32_t dt, void *d_out, int64_t ld) {
   c->last_call_first = (int)c->ev_log.size();
   const int l = p->k;
+  const bool rc = p->strands == 2;
   const int pa = std::max(1, maxlen_a - l + 1), pb = std::max(1, maxlen_b - l + 1);
   const int nba = gkmx_blocks(pa), nbb = gkmx_blocks(pb);
 
@@ -1886,14 +1905,14 @@ static int gkm_cross_device(kmg_ctx *c, const kmg_params *p, const GkmWeights &w
     KMG_TRY(c->diagv.ensure(sizeof(double) * (size_t)na));
     KMG_TRY(c->dsq.ensure(sizeof(double) * (size_t)nb));
     StageTimer t(c, ST_DIAG);
-    KMG_HIP(launch_gkmx_diag(A, l, wt, c->diagv.as<double>(), c->stream));
-    KMG_HIP(launch_gkmx_diag(B, l, wt, c->dsq.as<double>(), c->stream));
+    KMG_HIP(launch_gkmx_diag(A, l, rc, wt, c->diagv.as<double>(), c->stream));
+    KMG_HIP(launch_gkmx_diag(B, l, rc, wt, c->dsq.as<double>(), c->stream));
     o.normalize = 1;
     sa = c->diagv.as<double>();
     sb = c->dsq.as<double>();
   }
   StageTimer t(c, ST_GKMX);
-  KMG_HIP(launch_gram_gkmx(A, B, l, wt, o, sa, sb, c->stream));
+  KMG_HIP(launch_gram_gkmx(A, B, l, rc, wt, o, sa, sb, c->stream));
   return KMG_OK;
 }
 
@@ -1987,6 +2006,7 @@ struct kmg_scorer {
 
 static int scorer_check_params(const kmg_params *p) {
   if (!p) return fail(KMG_EINVAL, "params is NULL");
+  KMG_TRY(strands_check(p));
   if (p->kind == KMG_GKM) return fail(KMG_EUNSUPPORTED, "scorer: the gkm kernel (KMG_GKM) has no table scorer");
   if (p->kind != KMG_SPECTRUM && p->kind != KMG_MISMATCH)
     return fail(KMG_EUNSUPPORTED, "scorer: spectrum or mismatch only (kind %d)", p->kind);

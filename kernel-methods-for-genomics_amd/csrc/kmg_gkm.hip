@@ -37,6 +37,19 @@
 //           so both stores are row-contiguous; a diagonal tile computes j >= i and mirrors
 //           inside LDS.
 //   edges   rows past row1 and columns past n are not staged, computed or stored.
+//   RC      both strands (kmg_params.strands = 2, l <= 15):
+//             K2(x, y) = K(x, y) + K(x, rc(y)),  rc = reverse complement (code c -> c ^ 3)
+//           The l-mers of rc(y) are the reverse complements of the l-mers of y, so staging also
+//           writes the columns' reverse-complement words into a third LDS array [16][pp]
+//           (<= 16 KB more): (pairrev32(w) >> (32 - 2l)) ^ ((1 << 2l) - 1), KMG_INVALID kept.
+//           The inner step reads the forward and the reverse-complement 16-byte piece and adds
+//           both lookups; the two words are valid together, so the column select is shared.
+//           K2 is symmetric (ham(u, rc(v)) = ham(v, rc(u))), so SYM, the mirror and the
+//           transposed store are the single-strand ones.  K2 is half the inner product of the
+//           strand-symmetrised feature map c(x) + c(rc(x)); the factor 2 cancels under
+//           normalisation.  Still int32: 2 * 256^2 C(16, 8) < 2^31.  l = 16 is refused by the
+//           caller: rc(A^16) = T^16 is KMG_INVALID's bits, and dropping it on one strand only
+//           would break the symmetry SYM relies on.
 // gkm_diag_kernel: K_ii for the fused normalize_K, one wave a sequence, four a workgroup.
 #include "kmg_internal.h"
 #include "kmg_rowacc.h"
@@ -56,6 +69,13 @@ __device__ __forceinline__ uint32_t gkm_mask(int l) {
 __device__ __forceinline__ int gkm_dist(uint32_t a, uint32_t b, uint32_t maskAA, int base) {
   const uint32_t x = a ^ b;
   return __popc(((x << 1) | x) & maskAA) + base;
+}
+
+// reverse complement of an l-letter word (l <= 15), right-aligned like w; KMG_INVALID stays
+__device__ __forceinline__ uint32_t gkm_rcword(uint32_t w, int l) {
+  const uint32_t r = __builtin_bitreverse32(w);
+  const uint32_t pr = ((r & 0x55555555u) << 1) | ((r >> 1) & 0x55555555u);  // pairs reversed
+  return w == KMG_INVALID ? KMG_INVALID : (pr >> (32 - 2 * l)) ^ ((1u << (2 * l)) - 1u);
 }
 
 __device__ __forceinline__ void gkm_load_weights(const GkmWeights &wt, int32_t *w_s) {
@@ -81,7 +101,7 @@ __device__ __forceinline__ void gkm_emit(const OutSpec &o, int64_t il, int64_t i
   }
 }
 
-template <int NQ, bool SYM>
+template <int NQ, bool SYM, bool RC>
 __global__ __launch_bounds__(256) void gram_gkm_kernel(const uint32_t *__restrict__ words, int pmax,
                                                        int l, int64_t n, int64_t row0, int64_t rows,
                                                        int64_t tiles_c, GkmWeights wt, OutSpec o) {
@@ -89,7 +109,8 @@ __global__ __launch_bounds__(256) void gram_gkm_kernel(const uint32_t *__restric
   const int pp = (pmax + 3) & ~3;
   uint32_t *rw = gkm_lds;                                    // [16][pp] row words
   uint32_t *cwd = gkm_lds + GKM_T * pp;                      // [16][pp] column words
-  int32_t *w_s = (int32_t *)(gkm_lds + 2 * GKM_T * pp);      // [GKM_WTAB]
+  uint32_t *crc = gkm_lds + 2 * GKM_T * pp;                  // [16][pp] their rc words (RC)
+  int32_t *w_s = (int32_t *)(gkm_lds + (RC ? 3 : 2) * GKM_T * pp);  // [GKM_WTAB]
   int32_t *res = w_s + GKM_WTAB + 2;                         // [16][GKM_RES_LD]
 
   int64_t tr, tc;
@@ -116,7 +137,9 @@ __global__ __launch_bounds__(256) void gram_gkm_kernel(const uint32_t *__restric
     const bool row = s < GKM_T;
     const int sl = row ? s : s - GKM_T;
     const bool ok = a < pmax && sl < (row ? nr : nc);
-    gkm_lds[t] = ok ? words[((row ? i0 : j0) + sl) * pmax + a] : KMG_INVALID;
+    const uint32_t w = ok ? words[((row ? i0 : j0) + sl) * pmax + a] : KMG_INVALID;
+    gkm_lds[t] = w;
+    if (RC && !row) crc[sl * pp + a] = gkm_rcword(w, l);
   }
   __syncthreads();
 
@@ -140,12 +163,20 @@ __global__ __launch_bounds__(256) void gram_gkm_kernel(const uint32_t *__restric
       for (int b0 = 4 * half; b0 < pmax; b0 += 8) {
         const uint4 y4 = *(const uint4 *)(cs + b0);
         const uint32_t y[4] = {y4.x, y4.y, y4.z, y4.w};
+        uint32_t z[4] = {};
+        if constexpr (RC) {
+          const uint4 z4 = *(const uint4 *)(crc + c * pp + b0);
+          z[0] = z4.x, z[1] = z4.y, z[2] = z4.z, z[3] = z4.w;
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           int sw = 0;
 #pragma unroll
-          for (int q = 0; q < NQ; ++q) sw += w_s[gkm_dist(xa[q], y[e], maskAA, base[q])];
-          s += y[e] == KMG_INVALID ? 0 : sw;
+          for (int q = 0; q < NQ; ++q) {
+            sw += w_s[gkm_dist(xa[q], y[e], maskAA, base[q])];
+            if constexpr (RC) sw += w_s[gkm_dist(xa[q], z[e], maskAA, base[q])];
+          }
+          s += y[e] == KMG_INVALID ? 0 : sw;  // z[e] is invalid exactly when y[e] is
         }
       }
 #pragma unroll
@@ -178,6 +209,9 @@ __global__ __launch_bounds__(256) void gram_gkm_kernel(const uint32_t *__restric
 // K_ii = sum_{a, b} h[ham(x_a, x_b)] is symmetric in (a, b): the b > a half counted twice plus
 // the a = b term.  Lane t takes the words a = t and a = P - 1 - t (and so on in strides of
 // 128), whose tails add up to ~P iterations for every lane, as diag_ham_small_kernel does.
+// RC adds sum_{a, b} h[ham(x_a, rc(x_b))], symmetric in (a, b) as well (ham(u, rc(v)) =
+// ham(v, rc(u))): the same tails, with the a = b term h[ham(x_a, rc(x_a))] instead of h[0].
+template <bool RC>
 __global__ __launch_bounds__(256) void gkm_diag_kernel(const uint32_t *__restrict__ words, int pmax,
                                                        int l, int64_t n, GkmWeights wt,
                                                        double *__restrict__ diagv,
@@ -200,9 +234,12 @@ __global__ __launch_bounds__(256) void gkm_diag_kernel(const uint32_t *__restric
     const uint32_t xa = xk[a];
     if (xa == KMG_INVALID) return;
     s += w_s[0];  // b = a
+    if constexpr (RC) s += w_s[gkm_dist(xa, gkm_rcword(xa, l), maskAA, 0)];
     for (int b = a + 1; b < P; ++b) {
       const uint32_t yb = xk[b];
-      s += 2 * w_s[gkm_dist(xa, yb, maskAA, yb == KMG_INVALID ? 17 : 0)];
+      const int base = yb == KMG_INVALID ? 17 : 0;
+      s += 2 * w_s[gkm_dist(xa, yb, maskAA, base)];
+      if constexpr (RC) s += 2 * w_s[gkm_dist(xa, gkm_rcword(yb, l), maskAA, base)];
     }
   };
   for (int a0 = 0; a0 < (P + 1) / 2; a0 += 64) {
@@ -228,27 +265,28 @@ int64_t gkm_tiles(int64_t n, int64_t rows, bool sym) {
   return sym ? tc * (tc + 1) / 2 : trw * tc;
 }
 
-hipError_t launch_gram_gkm(const uint32_t *words, int pmax, int l, int64_t n, int64_t row0,
+hipError_t launch_gram_gkm(const uint32_t *words, int pmax, int l, bool rc, int64_t n, int64_t row0,
                            int64_t row1, bool sym, const GkmWeights &wt, const OutSpec &o,
                            hipStream_t s) {
   const int64_t rows = row1 - row0;
   if (rows <= 0 || n <= 0) return hipSuccess;
   if (pmax < 1 || pmax > 256 || l < 1 || l > 16) return hipErrorInvalidValue;
   if (sym && (row0 != 0 || rows != n)) return hipErrorInvalidValue;
+  if (rc && l > 15) return hipErrorInvalidValue;  // rc(A^16) would be KMG_INVALID
   const int64_t tiles = gkm_tiles(n, rows, sym);
   if (tiles >= KMG_GKM_MAX_TILES) return hipErrorInvalidValue;  // AQL grid size is 32-bit
   const int pp = (pmax + 3) & ~3;
-  const size_t lds = sizeof(uint32_t) * (size_t)(2 * GKM_T * pp + GKM_WTAB + 2 + GKM_T * GKM_RES_LD);
+  const size_t lds =
+      sizeof(uint32_t) * (size_t)((rc ? 3 : 2) * GKM_T * pp + GKM_WTAB + 2 + GKM_T * GKM_RES_LD);
   const dim3 grid((unsigned)tiles);
   const int64_t tiles_c = (n + GKM_T - 1) / GKM_T;
 #define KMG_GKM_LAUNCH(NQ_)                                                                        \
   do {                                                                                             \
-    if (sym)                                                                                       \
-      hipLaunchKernelGGL((gram_gkm_kernel<NQ_, true>), grid, dim3(256), lds, s, words, pmax, l, n, \
-                         row0, rows, tiles_c, wt, o);                                              \
-    else                                                                                           \
-      hipLaunchKernelGGL((gram_gkm_kernel<NQ_, false>), grid, dim3(256), lds, s, words, pmax, l,   \
-                         n, row0, rows, tiles_c, wt, o);                                           \
+    auto kern = gram_gkm_kernel<NQ_, false, false>;                                                \
+    if (sym) kern = rc ? gram_gkm_kernel<NQ_, true, true> : gram_gkm_kernel<NQ_, true, false>;     \
+    else if (rc) kern = gram_gkm_kernel<NQ_, false, true>;                                         \
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, words, pmax, l, n, row0, rows, tiles_c, wt,  \
+                       o);                                                                         \
   } while (0)
   const int nq = (pmax + 31) / 32;  // row words a lane
   if (nq <= 1) KMG_GKM_LAUNCH(1);
@@ -261,13 +299,14 @@ hipError_t launch_gram_gkm(const uint32_t *words, int pmax, int l, int64_t n, in
   return hipGetLastError();
 }
 
-hipError_t launch_gkm_diag(const uint32_t *words, int pmax, int l, int64_t n, const GkmWeights &wt,
-                           double *diagv, double *dsq, hipStream_t s) {
+hipError_t launch_gkm_diag(const uint32_t *words, int pmax, int l, bool rc, int64_t n,
+                           const GkmWeights &wt, double *diagv, double *dsq, hipStream_t s) {
   if (n <= 0) return hipSuccess;
-  if (pmax < 1 || pmax > 256 || l < 1 || l > 16) return hipErrorInvalidValue;
+  if (pmax < 1 || pmax > 256 || l < 1 || l > 16 || (rc && l > 15)) return hipErrorInvalidValue;
   const size_t lds = sizeof(uint32_t) * (size_t)(4 * pmax + GKM_WTAB);
-  hipLaunchKernelGGL(gkm_diag_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), lds, s, words, pmax,
-                     l, n, wt, diagv, dsq);
+  hipLaunchKernelGGL(rc ? gkm_diag_kernel<true> : gkm_diag_kernel<false>,
+                     dim3((unsigned)((n + 3) / 4)), dim3(256), lds, s, words, pmax, l, n, wt, diagv,
+                     dsq);
   return hipGetLastError();
 }
 

@@ -19,7 +19,7 @@
 //
 // gkmx_extract_kernel   packed records -> words [n][32 nblk] (0 where invalid) and validity
 //                       bits [n][nblk], nblk = ceil(pmax / 32) blocks of 32 words a row.
-// gram_gkmx_kernel<DIAG, TWO>   one 256-thread workgroup a tile of 16 rows x 8 columns.
+// gram_gkmx_kernel<DIAG, TWO, RC>   one 256-thread workgroup a tile of 16 rows x 8 columns.
 //   LDS     one chunk of 8 blocks (256 words) of every tile row and column, 4 B a word:
 //           16 KB + 8 KB, their validity words (768 B), hm (80 B) and the int64 result tile
 //           (1 KB): 26 KB whatever pmax is.  The chunk loops (A chunks outside, B chunks
@@ -43,6 +43,26 @@
 //           converted once to the output type.
 //   DIAG    pairs (i, i): a tile is 8 rows, staged on both sides; wave w owns rows 2w, 2w + 1
 //           and sweeps each against itself.  Writes sqrt(K_ii) (IEEE) for the normalisation.
+//   RC      both strands (kmg_params.strands = 2):
+//             K2(x, y) = K(x, y) + K(x, rc(y)) = sum_{a, b} (h[ham(x_a, y_b)] + h[ham(x_a, rc(y_b))])
+//           rc = reverse complement (letters reversed, code c -> c ^ 3).  The words of rc(y) are
+//           the reverse complements of the words of y, valid together, so staging and
+//           extraction are the single-strand ones and the second B operand is made in
+//           registers from the same ds_read_b32: with the word right-aligned in 2l bits, its
+//           left-aligned reverse complement is pairrev32(w) ^ (~0u << (32 - 2l)) (pairrev32:
+//           v_bfrev_b32, then the two bits of every pair swapped), expanded by the routine that
+//           expands every other operand.  An invalid word is stored as 0 and its reverse
+//           complement is not 0, so that operand takes the forward one's validity handling
+//           (empty block skipped, full block as is, mixed block masked).  K2 is symmetric
+//           (ham(u, rc(v)) = ham(v, rc(u))) and is half the inner product of the
+//           strand-symmetrised feature map c(x) + c(rc(x)); the factor 2 cancels under
+//           normalisation, whose diagonals sqrt(K2_ii) carry their own reverse-complement term.
+//           Two accumulator sets: per (row, B block) the forward MFMAs go into one v16i and the
+//           reverse-complement ones into a second, issued in the order F0 | R0, look up F0,
+//           F1, look up R0 | R1, look up F1, ... so that one set's 16 lookups run while the
+//           other set's MFMA is in flight.  Both sets' lookups add into one int32 partial (at
+//           most 32 adds of <= 12870) before the flush into the lane's int64: the flush rule
+//           holds with twice the count.
 #include "kmg_internal.h"
 
 namespace kmg {
@@ -93,10 +113,10 @@ struct GxLane {
   int lsh, sh0, sh1, lr;      // left-align shift, the two steps' letter-group shifts, word slot
 };
 
-// the lane's one-hot dwords of word w: x0 = MFMA step 0, x1 = step 1
+// the lane's one-hot dwords of the left-aligned word wl (letter p at bits 31 - 2p, 30 - 2p):
+// x0 = MFMA step 0, x1 = step 1
 template <bool TWO>
-__device__ __forceinline__ void gx_expand(const GxLane<TWO> &L, uint32_t w, v4i &x0, v4i &x1) {
-  const uint32_t wl = w << L.lsh;
+__device__ __forceinline__ void gx_expand_left(const GxLane<TWO> &L, uint32_t wl, v4i &x0, v4i &x1) {
   const uint32_t g0 = wl >> L.sh0;  // the group's 4 letters at bits 7..0 (bits above are masked)
   x0[0] = (int)(L.val[0] << ((g0 >> 3) & 24u));
   x0[1] = (int)(L.val[1] << ((g0 >> 1) & 24u));
@@ -113,6 +133,18 @@ __device__ __forceinline__ void gx_expand(const GxLane<TWO> &L, uint32_t w, v4i 
   }
 }
 
+// ... of the word w as extracted (right-aligned in 2l bits)
+template <bool TWO>
+__device__ __forceinline__ void gx_expand(const GxLane<TWO> &L, uint32_t w, v4i &x0, v4i &x1) {
+  gx_expand_left<TWO>(L, w << L.lsh, x0, x1);
+}
+
+// the 16 two-bit pairs of x in reverse order
+__device__ __forceinline__ uint32_t gx_pairrev32(uint32_t x) {
+  const uint32_t r = __builtin_bitreverse32(x);
+  return ((r & 0x55555555u) << 1) | ((r >> 1) & 0x55555555u);
+}
+
 template <bool TWO>
 __device__ __forceinline__ void gx_mask(const GxLane<TWO> &L, uint32_t vw, v4i &x0, v4i &x1) {
   const int m = -(int)((vw >> L.lr) & 1u);
@@ -120,8 +152,24 @@ __device__ __forceinline__ void gx_mask(const GxLane<TWO> &L, uint32_t vw, v4i &
   if constexpr (TWO) x1 &= m;
 }
 
-// NR rows' operands of one A block against the nbb staged blocks of one column
-template <int NR, bool TWO>
+// one MFMA result: acc[e] = 4 * matches, the byte offset into hm
+template <bool TWO>
+__device__ __forceinline__ v16i gx_mfma(const v4i &a0, const v4i &a1, const v4i &b0, const v4i &b1) {
+  v16i acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b0, (v16i){}, 0, 0, 0);
+  if constexpr (TWO) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b1, acc, 0, 0, 0);
+  return acc;
+}
+
+__device__ __forceinline__ int gx_lookup(const int32_t *hm, const v16i &acc) {
+  int t = 0;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) t += *(const int32_t *)((const char *)hm + acc[e]);
+  return t;
+}
+
+// NR rows' operands of one A block against the nbb staged blocks of one column; RC: against
+// both strands of the column, two accumulator sets (f forward, g reverse complement)
+template <int NR, bool TWO, bool RC>
 __device__ __forceinline__ void gx_sweep(const GxLane<TWO> &L, const v4i (&a0)[NR],
                                          const v4i (&a1)[NR], const uint32_t *wcol,
                                          const uint32_t *vcol, int nbb, const int32_t *hm,
@@ -130,21 +178,30 @@ __device__ __forceinline__ void gx_sweep(const GxLane<TWO> &L, const v4i (&a0)[N
     const uint32_t vw = __builtin_amdgcn_readfirstlane(vcol[bb]);
     if (vw == 0u) continue;
     v4i b0, b1;
-    gx_expand<TWO>(L, wcol[bb * 32 + L.lr], b0, b1);
+    const uint32_t w = wcol[bb * 32 + L.lr];
+    gx_expand<TWO>(L, w, b0, b1);
     if (vw != 0xFFFFFFFFu) gx_mask<TWO>(L, vw, b0, b1);
+    if constexpr (!RC) {
 #pragma unroll
-    for (int r = 0; r < NR; ++r) {
-      v16i acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0[r], b0, (v16i){}, 0, 0, 0);
-      if constexpr (TWO) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1[r], b1, acc, 0, 0, 0);
-      int t = 0;  // acc[e] = 4 * matches: the byte offset into hm
+      for (int r = 0; r < NR; ++r) S[r] += gx_lookup(hm, gx_mfma<TWO>(a0[r], a1[r], b0, b1));
+    } else {
+      v4i c0, c1;
+      gx_expand_left<TWO>(L, gx_pairrev32(w) ^ (0xFFFFFFFFu << L.lsh), c0, c1);
+      if (vw != 0xFFFFFFFFu) gx_mask<TWO>(L, vw, c0, c1);
+      v16i f = gx_mfma<TWO>(a0[0], a1[0], b0, b1);
 #pragma unroll
-      for (int e = 0; e < 16; ++e) t += *(const int32_t *)((const char *)hm + acc[e]);
-      S[r] += t;
+      for (int r = 0; r < NR; ++r) {
+        const v16i g = gx_mfma<TWO>(a0[r], a1[r], c0, c1);  // in flight under f's lookups
+        int t = gx_lookup(hm, f);
+        if (r + 1 < NR) f = gx_mfma<TWO>(a0[r + 1], a1[r + 1], b0, b1);  // ... under g's
+        t += gx_lookup(hm, g);
+        S[r] += t;  // <= 32 adds of <= 12870 in the int32
+      }
     }
   }
 }
 
-template <bool DIAG, bool TWO>
+template <bool DIAG, bool TWO, bool RC>
 __global__ __launch_bounds__(256) void gram_gkmx_kernel(GkmxSide A, GkmxSide B, int l, int64_t row0,
                                                         int64_t rows, int64_t tiles_c,
                                                         GkmWeights wt, OutSpec o,
@@ -237,7 +294,7 @@ __global__ __launch_bounds__(256) void gram_gkmx_kernel(GkmxSide A, GkmxSide B, 
             v4i a0[1], a1[1];
             gx_expand<TWO>(L, wa[r][ab * 32 + L.lr], a0[0], a1[0]);
             gx_mask<TWO>(L, vw, a0[0], a1[0]);
-            gx_sweep<1, TWO>(L, a0, a1, wb[r], vb[r], nbb, hm, S[rr]);
+            gx_sweep<1, TWO, RC>(L, a0, a1, wb[r], vb[r], nbb, hm, S[rr]);
           }
         }
       } else {
@@ -256,7 +313,7 @@ __global__ __launch_bounds__(256) void gram_gkmx_kernel(GkmxSide A, GkmxSide B, 
             if (__builtin_amdgcn_readfirstlane(any) == 0u) continue;
 #pragma unroll
             for (int c = 0; c < GX_TC; ++c)
-              if (c < nc) gx_sweep<4, TWO>(L, a0, a1, wb[c], vb[c], nbb, hm, S[c]);
+              if (c < nc) gx_sweep<4, TWO, RC>(L, a0, a1, wb[c], vb[c], nbb, hm, S[c]);
           }
         }
       }
@@ -279,7 +336,7 @@ __global__ __launch_bounds__(256) void gram_gkmx_kernel(GkmxSide A, GkmxSide B, 
   __syncthreads();
 
   if constexpr (DIAG) {
-    if (tid < nr) dsq_out[i0 + tid] = __builtin_sqrt((double)res[tid][0]);  // IEEE sqrt
+    if (tid < nr) dsq_out[i0 + tid] = __builtin_sqrt((double)res[tid][0]);  // IEEE sqrt (RC: K2_ii)
   } else {
     const int r = tid / GX_TC, c = tid % GX_TC;
     if (tid < GX_TR * GX_TC && r < nr && c < nc) {
@@ -310,8 +367,9 @@ hipError_t launch_gkmx_extract(const Packed &pk, int64_t n, int l, int pmax, uin
   return hipGetLastError();
 }
 
-hipError_t launch_gram_gkmx(const GkmxSide &A, const GkmxSide &B, int l, const GkmWeights &wt,
-                            const OutSpec &o, const double *sa, const double *sb, hipStream_t s) {
+hipError_t launch_gram_gkmx(const GkmxSide &A, const GkmxSide &B, int l, bool rc,
+                            const GkmWeights &wt, const OutSpec &o, const double *sa,
+                            const double *sb, hipStream_t s) {
   if (A.n <= 0 || B.n <= 0) return hipSuccess;
   if (l < 1 || l > 16 || A.nblk < 1 || B.nblk < 1) return hipErrorInvalidValue;
   if (o.normalize && (!sa || !sb)) return hipErrorInvalidValue;
@@ -319,38 +377,34 @@ hipError_t launch_gram_gkmx(const GkmxSide &A, const GkmxSide &B, int l, const G
   if (tiles_c >= KMG_GKM_MAX_TILES) return hipErrorInvalidValue;  // AQL grid size is 32-bit
   const int64_t max_rows = (KMG_GKM_MAX_TILES - 1) / tiles_c * GX_TR;
   const size_t esz = o.dtype == KMG_F64 ? 8 : 4;
+  auto kern = gram_gkmx_kernel<false, false, false>;
+  if (l > 8) kern = rc ? gram_gkmx_kernel<false, true, true> : gram_gkmx_kernel<false, true, false>;
+  else if (rc) kern = gram_gkmx_kernel<false, false, true>;
   for (int64_t r0 = 0; r0 < A.n; r0 += max_rows) {
     const int64_t rows = A.n - r0 < max_rows ? A.n - r0 : max_rows;
     const dim3 grid((unsigned)((rows + GX_TR - 1) / GX_TR * tiles_c));
     OutSpec os = o;
     os.out = (char *)o.out + (size_t)r0 * o.ld * esz;
-    if (l > 8)
-      hipLaunchKernelGGL((gram_gkmx_kernel<false, true>), grid, dim3(256), 0, s, A, B, l, r0, rows,
-                         tiles_c, wt, os, sa, sb, (double *)nullptr);
-    else
-      hipLaunchKernelGGL((gram_gkmx_kernel<false, false>), grid, dim3(256), 0, s, A, B, l, r0, rows,
-                         tiles_c, wt, os, sa, sb, (double *)nullptr);
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, A, B, l, r0, rows, tiles_c, wt, os, sa, sb,
+                       (double *)nullptr);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
 
-hipError_t launch_gkmx_diag(const GkmxSide &A, int l, const GkmWeights &wt, double *dsq,
+hipError_t launch_gkmx_diag(const GkmxSide &A, int l, bool rc, const GkmWeights &wt, double *dsq,
                             hipStream_t s) {
   if (A.n <= 0) return hipSuccess;
   if (l < 1 || l > 16 || A.nblk < 1) return hipErrorInvalidValue;
   const int64_t tiles = (A.n + GX_TC - 1) / GX_TC;
   if (tiles >= KMG_GKM_MAX_TILES) return hipErrorInvalidValue;
   const OutSpec o{};
-  if (l > 8)
-    hipLaunchKernelGGL((gram_gkmx_kernel<true, true>), dim3((unsigned)tiles), dim3(256), 0, s, A, A,
-                       l, (int64_t)0, A.n, (int64_t)1, wt, o, (const double *)nullptr,
-                       (const double *)nullptr, dsq);
-  else
-    hipLaunchKernelGGL((gram_gkmx_kernel<true, false>), dim3((unsigned)tiles), dim3(256), 0, s, A, A,
-                       l, (int64_t)0, A.n, (int64_t)1, wt, o, (const double *)nullptr,
-                       (const double *)nullptr, dsq);
+  auto kern = gram_gkmx_kernel<true, false, false>;
+  if (l > 8) kern = rc ? gram_gkmx_kernel<true, true, true> : gram_gkmx_kernel<true, true, false>;
+  else if (rc) kern = gram_gkmx_kernel<true, false, true>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), 0, s, A, A, l, (int64_t)0, A.n,
+                     (int64_t)1, wt, o, (const double *)nullptr, (const double *)nullptr, dsq);
   return hipGetLastError();
 }
 

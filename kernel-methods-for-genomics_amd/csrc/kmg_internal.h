@@ -288,12 +288,13 @@ struct GkmWeights {
 #define KMG_GKM_MAX_TILES ((int64_t)1 << 24)
 int64_t gkm_tiles(int64_t n, int64_t rows, bool sym);
 // rows [row0, row1) x all n columns at o.out; sym (row0 = 0, row1 = n only): the upper block
-// triangle is computed and every off-diagonal tile stored twice
-hipError_t launch_gram_gkm(const uint32_t *words, int pmax, int l, int64_t n, int64_t row0,
+// triangle is computed and every off-diagonal tile stored twice.  rc (l <= 15 only): both
+// strands, K2(x, y) = K(x, y) + K(x, rc(y)), in the Gram and in the diagonal
+hipError_t launch_gram_gkm(const uint32_t *words, int pmax, int l, bool rc, int64_t n, int64_t row0,
                            int64_t row1, bool sym, const GkmWeights &wt, const OutSpec &o,
                            hipStream_t s);
-hipError_t launch_gkm_diag(const uint32_t *words, int pmax, int l, int64_t n, const GkmWeights &wt,
-                           double *diagv, double *dsq, hipStream_t s);
+hipError_t launch_gkm_diag(const uint32_t *words, int pmax, int l, bool rc, int64_t n,
+                           const GkmWeights &wt, double *diagv, double *dsq, hipStream_t s);
 
 // ---------------------------------------------------------------- gkm cross (kmg_gkmx.hip)
 // rectangular gkm block Kx[i][j] = sum_{a,b} h[ham(A_i word a, B_j word b)] on int8 MFMA, rows
@@ -310,10 +311,13 @@ hipError_t launch_gkmx_extract(const Packed &pk, int64_t n, int l, int pmax, uin
                                uint32_t *bits, hipStream_t s);
 // all A.n x B.n pairs at o.out (o.out, o.ld, o.dtype, o.normalize are read); normalised:
 // raw / (sa[i] * sb[j]).  Rows are split so every launch stays below KMG_GKM_MAX_TILES tiles.
-hipError_t launch_gram_gkmx(const GkmxSide &A, const GkmxSide &B, int l, const GkmWeights &wt,
-                            const OutSpec &o, const double *sa, const double *sb, hipStream_t s);
-// dsq[i] = sqrt(K(A_i, A_i)), from the same kernel over the pairs (i, i)
-hipError_t launch_gkmx_diag(const GkmxSide &A, int l, const GkmWeights &wt, double *dsq,
+// rc: both strands, Kx(A_i, B_j) + Kx(A_i, rc(B_j)), from the same words and bits.
+hipError_t launch_gram_gkmx(const GkmxSide &A, const GkmxSide &B, int l, bool rc,
+                            const GkmWeights &wt, const OutSpec &o, const double *sa,
+                            const double *sb, hipStream_t s);
+// dsq[i] = sqrt(K(A_i, A_i)) (rc: of the both-strands K2), from the same kernel over the
+// pairs (i, i)
+hipError_t launch_gkmx_diag(const GkmxSide &A, int l, bool rc, const GkmWeights &wt, double *dsq,
                             hipStream_t s);
 
 // ---------------------------------------------------------------- scorer (kmg_score.hip)

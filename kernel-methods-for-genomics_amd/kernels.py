@@ -71,19 +71,19 @@ def get_gappy_K(X, k, g):
     return _eng().gappy(_seqs(X), k, g)
 
 
-def get_gkm_K(X, l, k, d=None):
+def get_gkm_K(X, l, k, d=None, *, both_strands=False):
     """Gapped k-mer kernel of gkm-SVM (word length l, k informative positions, truncation d;
     d=None is min(3, l - k)), normalised.  Not in the reference: ``select_method`` has no
     method string for it."""
-    return _eng().gkm(_seqs(X), l, k, d)
+    return _eng().gkm(_seqs(X), l, k, d, both_strands=both_strands)
 
 
-def get_gkm_cross_K(Xa, Xb, l, k, d=None):
+def get_gkm_cross_K(Xa, Xb, l, k, d=None, *, both_strands=False):
     """Gapped k-mer block K(Xa rows, Xb rows), normalised by both sides' own diagonals: the
     K(queries, support vectors) of gkm-SVM prediction, rows of any length.
     ``get_gkm_cross_K(X, X, ...)`` is the square gkm Gram of rows too long for ``get_gkm_K``
     (its diagonal is K_ii / (s_i s_i), 1 up to one rounding, not filled in)."""
-    return _eng().gkm_cross(_seqs(Xa), _seqs(Xb), l, k, d)
+    return _eng().gkm_cross(_seqs(Xa), _seqs(Xb), l, k, d, both_strands=both_strands)
 
 
 # ----------------------------------------------------------------------- helpers

@@ -179,13 +179,19 @@ class GramEngine:
             gappy_reference_errors(len(s), k, g)
         return self._run(P.make(L.KMG_GAPPY, k=k, g=g, window=101), seqs)
 
-    def gkm(self, seqs, l, k, d=None, normalize=True, out_dtype=L.KMG_F64):
+    def gkm(self, seqs, l, k, d=None, normalize=True, out_dtype=L.KMG_F64, *, both_strands=False):
         """Gapped k-mer kernel of gkm-SVM / LS-GKM (Ghandi et al. 2014; no reference
         counterpart): K_ij = sum_{a,b} h[ham(x_i[a:a+l], x_j[b:b+l])], h[m] = C(l - m, k) for
         m <= d, over the all-ACGT words of the whole rows (a word holding any other character
         is not counted); d=None is min(3, l - k).  normalize=True applies normalize_K, and a
-        sequence without a valid word (its K_ii would be 0) raises ValueError."""
-        p = P.gkm(l, k, d, normalize)
+        sequence without a valid word (its K_ii would be 0) raises ValueError.
+        both_strands=True counts a word together with its reverse complement, as gkm-SVM does
+        by default: K(x, y) + K(x, rc(y)), symmetric, the diagonals of normalize_K included.
+        It needs l <= 15 here (ValueError otherwise); ``gkm_cross`` serves l = 16."""
+        p = P.gkm(l, k, d, normalize, both_strands)
+        if both_strands and int(l) == 16:
+            raise ValueError("gkm: both_strands=True at l=16 is served by gkm_cross only (the "
+                             "reverse complement of A*16 is the square path's invalid-word marker)")
         seqs = list(seqs)
         if normalize:
             if out_dtype == L.KMG_I32:
@@ -197,14 +203,17 @@ class GramEngine:
                                      "its diagonal would be 0 under normalize=True")
         return self._run(p, seqs, out_dtype)
 
-    def gkm_cross(self, seqs_a, seqs_b, l, k, d=None, normalize=True, out_dtype=L.KMG_F64):
+    def gkm_cross(self, seqs_a, seqs_b, l, k, d=None, normalize=True, out_dtype=L.KMG_F64, *,
+                  both_strands=False):
         """Rectangular gapped k-mer block [len(seqs_a), len(seqs_b)]:
         K_ij = sum_{a,b} h[ham(A_i[a:a+l], B_j[b:b+l])] with ``gkm``'s h and word rules, rows
         of any length, T^16 counted (kmg_gkm_cross: int8 MFMA).  This is K(queries, support
         vectors) for prediction; ``gkm_cross(s, s)`` is the way to a square gkm Gram of rows
         longer than ``gkm`` takes.  normalize=True divides by sqrt(K(A_i, A_i) K(B_j, B_j)),
-        and a row without a valid word on either side raises ValueError."""
-        p = P.gkm(l, k, d, normalize)
+        and a row without a valid word on either side raises ValueError.  both_strands=True:
+        K(A_i, B_j) + K(A_i, rc(B_j)) in one pass over the same staged words (l = 16 included),
+        normalised by the both-strands diagonals."""
+        p = P.gkm(l, k, d, normalize, both_strands)
         seqs_a, seqs_b = list(seqs_a), list(seqs_b)
         if normalize:
             if out_dtype == L.KMG_I32:

@@ -43,10 +43,11 @@ def gkm_weights(l, k, d):
     return [comb(l - m, k) if m <= d else 0 for m in range(l + 1)]
 
 
-def gkm(l, k, d=None, normalize=True):
+def gkm(l, k, d=None, normalize=True, both_strands=False):
     """KmgParams of the gapped k-mer kernel: word length l (1..16), k informative positions
     (1..l), truncation d (0..l - k; None = min(3, l - k), gkm-SVM's default).  The struct
-    carries them as k = l, g = l - k, m = d."""
+    carries them as k = l, g = l - k, m = d.  both_strands=True (strands = 2) counts every word
+    together with its reverse complement: K(x, y) + K(x, rc(y)), gkm-SVM's default."""
     l, k = int(l), int(k)
     if not 1 <= l <= 16:
         raise ValueError(f"gkm: word length l={l} outside 1..16")
@@ -55,14 +56,16 @@ def gkm(l, k, d=None, normalize=True):
     d = min(3, l - k) if d is None else int(d)
     if not 0 <= d <= l - k:
         raise ValueError(f"gkm: truncation d={d} outside 0..l-k (l-k={l - k})")
-    return make(L.KMG_GKM, k=l, g=l - k, m=d, normalize=1 if normalize else 0)
+    return make(L.KMG_GKM, k=l, g=l - k, m=d, normalize=1 if normalize else 0,
+                strands=2 if both_strands else 0)
 
 
 def make(kind, **kw):
     """Fill a KmgParams struct."""
     p = L.KmgParams()
     p.kind = kind
-    for name in ("k", "m", "d", "S", "g", "window", "normalize", "smith", "la_mode", "span"):
+    for name in ("k", "m", "d", "S", "g", "window", "normalize", "smith", "la_mode", "span",
+                 "strands"):
         if name in kw:
             setattr(p, name, int(kw[name]))
     if "lbda" in kw:

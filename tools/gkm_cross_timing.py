@@ -10,6 +10,13 @@ Both alternate in one process after a warm-up of each; the kernel stage of every
 by the library's device events.  A sample of the cross result is checked against the formula at
 the timed sizes.  One point has no yardstick: 256 rows of 1000 letters against themselves,
 reported as word pairs a second.  One JSON file.
+
+--strands runs the both-strands comparison of DESIGN.md §6f instead and writes
+profiles/gkm_strands_timing.json: at the same sizes, one both-strands call (strands = 2) of rows
+[0, N/2) x [N/2, N) against the two single-strand calls that compute the same thing (B, and B
+reverse-complemented on the host), "gkmx" stages, alternated in one process; and at the first
+size one both-strands square call (kmg_gram_device, all rows, SYM) against twice the
+single-strand "gkm" stage.  A both-strands call counts two evaluations a word pair.
 """
 import argparse
 import ctypes
@@ -108,15 +115,97 @@ def run_long(ctx, n, length, reps, rng):
             "sampled_entries_wrong": bad, "sampled_entries": cnt}
 
 
+def run_strands(ctx, n, reps, rng):
+    """cross: both-strands gkmx stage vs the sum of the two single-strand ones (B and rc(B))."""
+    codes, lens = E.synthetic(n, 101, seed=5)
+    ldc, h = codes.shape[1], n // 2
+    rcb = np.ascontiguousarray(codes[h:, ::-1] ^ 3)  # every row is ldc = 101 letters long
+    d_codes, d_lens, d_rcb = ctx.dmalloc(codes.nbytes), ctx.dmalloc(lens.nbytes), ctx.dmalloc(rcb.nbytes)
+    d_K = ctx.dmalloc(4 * h * (n - h))
+    ctx.h2d(d_codes, codes)
+    ctx.h2d(d_lens, lens)
+    ctx.h2d(d_rcb, rcb)
+    p1, p2 = P.gkm(LW, KI, D, normalize=False), P.gkm(LW, KI, D, normalize=False, both_strands=True)
+    ctx.set_timing(True)
+    routes = {"fwd": (p1, at(d_codes, h * ldc)), "rc": (p1, d_rcb), "both": (p2, at(d_codes, h * ldc))}
+    dev = {r: [] for r in routes}
+    for rep in range(reps + 1):  # one warm-up round of every route; "both" last: it is checked
+        for r, (p, d_b) in routes.items():
+            ctx.gkm_cross_device(p, d_codes, d_lens, h, ldc, d_b, at(d_lens, 4 * h), n - h, ldc,
+                                 L.KMG_I32, d_K, n - h)
+            ctx.synchronize()
+            if rep >= 1:
+                dev[r].append(ctx.stage_ms("gkmx"))
+    K = ctx.d2h(np.empty((h, n - h), dtype=np.int32), d_K)
+    pairs = [(0, 0), (h - 1, n - h - 1)] + [(int(rng.integers(0, h)), int(rng.integers(0, n - h)))
+                                            for _ in range(30)]
+    bad = sum(int(K[i, j]) != formula(codes[i], codes[h + j]) + formula(codes[i], rcb[j])
+              for i, j in pairs)
+    for d in (d_codes, d_lens, d_rcb, d_K):
+        ctx.dfree(d)
+    pw = 101 - LW + 1
+    evals = 2 * h * (n - h) * pw * pw  # two evaluations a word pair
+    med = {r: float(np.median(v)) for r, v in dev.items()}
+    two = med["fwd"] + med["rc"]
+    return {"n": n, "reps": reps, "stage_ms_median": med, "stage_ms_all": dev,
+            "two_single_strand_calls_ms": two, "ratio_both_over_two_calls": med["both"] / two,
+            "evaluations": evals, "evaluations_per_s": {"both": evals / (med["both"] * 1e-3),
+                                                        "two_calls": evals / (two * 1e-3)},
+            "sampled_entries_wrong": bad, "sampled_entries": len(pairs)}
+
+
+def run_strands_square(ctx, n, reps, rng):
+    """square: one both-strands kmg_gram_device call (SYM) vs twice the single-strand stage."""
+    codes, lens = E.synthetic(n, 101, seed=5)
+    ldc = codes.shape[1]
+    d_codes, d_lens, d_K = ctx.dmalloc(codes.nbytes), ctx.dmalloc(lens.nbytes), ctx.dmalloc(4 * n * n)
+    ctx.h2d(d_codes, codes)
+    ctx.h2d(d_lens, lens)
+    routes = {"one": P.gkm(LW, KI, D, normalize=False),
+              "both": P.gkm(LW, KI, D, normalize=False, both_strands=True)}
+    ctx.set_timing(True)
+    dev = {r: [] for r in routes}
+    for rep in range(reps + 1):
+        for r, p in routes.items():
+            ctx.gram_device(p, d_codes, d_lens, n, ldc, 0, n, L.KMG_I32, d_K, n)
+            ctx.synchronize()
+            if rep >= 1:
+                dev[r].append(ctx.stage_ms("gkm"))
+    K = ctx.d2h(np.empty((n, n), dtype=np.int32), d_K)
+    pairs = [(0, 0), (n - 1, 0)] + [(int(rng.integers(0, n)), int(rng.integers(0, n))) for _ in range(30)]
+    bad = sum(int(K[i, j]) != formula(codes[i], codes[j]) + formula(codes[i], codes[j, ::-1] ^ 3)
+              for i, j in pairs)
+    for d in (d_codes, d_lens, d_K):
+        ctx.dfree(d)
+    med = {r: float(np.median(v)) for r, v in dev.items()}
+    return {"n": n, "reps": reps, "stage_ms_median": med, "stage_ms_all": dev,
+            "twice_single_strand_ms": 2 * med["one"],
+            "ratio_both_over_twice_single": med["both"] / (2 * med["one"]),
+            "sampled_entries_wrong": bad, "sampled_entries": len(pairs)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gkm_cross_timing.json"))
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--sizes", default="2000,9000")
     ap.add_argument("--long", default="256x1000")
+    ap.add_argument("--strands", action="store_true",
+                    help="the both-strands comparison (DESIGN.md §6f) instead of the routes above")
     a = ap.parse_args()
     ctx = L.Context(0)
     rng = np.random.default_rng(12)
+    if a.strands:
+        sizes = [int(n) for n in a.sizes.split(",")]
+        res = {"l": LW, "k": KI, "d": D, "cross": [run_strands(ctx, n, a.reps, rng) for n in sizes],
+               "square": run_strands_square(ctx, sizes[0], a.reps, rng)}
+        ctx.close()
+        out = a.out.replace("gkm_cross_timing.json", "gkm_strands_timing.json")
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps([{k: v for k, v in r.items() if k != "stage_ms_all"}
+                          for r in res["cross"] + [res["square"]]]))
+        return
     res = [run(ctx, int(n), a.reps, rng) for n in a.sizes.split(",")]
     ln, ll = (int(v) for v in a.long.split("x"))
     long_res = run_long(ctx, ln, ll, a.reps, rng)
