@@ -185,6 +185,42 @@ int kmg_gkm_cross_device(kmg_ctx *ctx, const kmg_params *p, const uint8_t *d_cod
                          int64_t ldc_b, int32_t out_dtype, void *d_out, int64_t ld_out);
 
 /*
+ * Position-weighted gapped k-mer block (the centre-weighted wgkm kernel of LS-GKM): every word
+ * carries an integer weight 0..255 that depends on where it starts in its row, and a word pair
+ * counts with the product of the two weights,
+ *   out[i][j] = sum_{a, b} wts_a[i][a] wts_b[j][b] h[ham(A_i[a:a+l], B_j[b:b+l])]
+ * wts_x is uint8 [n][ldw_x]: the weight of the word that starts at letter a of row i is at
+ * [i][a] (entries past a row's last word are not read), ldw_x at least the longest row's word
+ * count (else KMG_EINVAL); weight 0 excludes a word.  wts_x = NULL: all ones on that side (ldw_x
+ * is not read); with both NULL the result is bit for bit that of kmg_gkm_cross.  p->strands = 2:
+ * a reverse-complement word takes the weight of the window it was made from,
+ *   sum_{a, b} wts_a[i][a] wts_b[j][b] (h[ham(A_i word a, B_j word b)] + h[ham(A_i word a, rc(B_j word b))])
+ * which is symmetric in (A_i, B_j).  Everything else follows kmg_gkm_cross (kinds, normalize,
+ * empty sides, dtype rules), with the weights counted: p->normalize = 1 divides by
+ * sqrt(Kw(A_i, A_i)) * sqrt(Kw(B_j, B_j)), each diagonal with its own side's weights on both of
+ * its sides (a row whose words all weigh 0 gives NaN), and with W_x = 255 for a weighted side, 1
+ * otherwise, strands W_a W_b P_a P_b h[0] >= 2^53 (under normalize = 1 also a diagonal's
+ * strands W_x^2 P_x^2 h[0]) is KMG_EUNSUPPORTED and KMG_I32 with that product >= 2^31 is
+ * KMG_EINVAL, all of it checked before any allocation or launch.  The weights are applied to
+ * the table lookups of the int8 MFMA results in int32 partials, flushed into int64
+ * (gram_gkmx_kernel<.., WT>, kmg_gkmx.hip); the raw values are exact integers.  The kernel time
+ * counts under stage "gkmx".  Host buffers in and out, synchronous.
+ */
+int kmg_gkm_cross_w(kmg_ctx *ctx, const kmg_params *p, const uint8_t *codes_a,
+                    const int32_t *lens_a, int64_t na, int64_t ldc_a, const uint8_t *wts_a,
+                    int64_t ldw_a, const uint8_t *codes_b, const int32_t *lens_b, int64_t nb,
+                    int64_t ldc_b, const uint8_t *wts_b, int64_t ldw_b, int32_t out_dtype,
+                    void *out, int64_t ld_out);
+/* The same on device pointers (rows up to ldc_a / ldc_b symbols bound the checks above, ldw_x
+ * included), on the context stream, without synchronising. */
+int kmg_gkm_cross_w_device(kmg_ctx *ctx, const kmg_params *p, const uint8_t *d_codes_a,
+                           const int32_t *d_lens_a, int64_t na, int64_t ldc_a,
+                           const uint8_t *d_wts_a, int64_t ldw_a, const uint8_t *d_codes_b,
+                           const int32_t *d_lens_b, int64_t nb, int64_t ldc_b,
+                           const uint8_t *d_wts_b, int64_t ldw_b, int32_t out_dtype, void *d_out,
+                           int64_t ld_out);
+
+/*
  * Device-resident column block: K[i][col0 + j] for every row i in [0, n) and j in
  * [0, col1 - col0), at d_out[i * ld_out + j].  K is symmetric, so this is the row slab
  * [col0, col1) x all n transposed: one GPU's 1/G share of a sharded build (the pair loops

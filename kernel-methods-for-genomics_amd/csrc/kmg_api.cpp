@@ -245,6 +245,8 @@ struct kmg_ctx {
   DevBuf sc_fix, sc_tab;            // kmg_scorer_create: fixed-point weights, the DP tables
   DevBuf gx_words_b, gx_bits;       // kmg_gkm_cross: side B's words (side A's are in kmers),
                                     // the validity bits of A, then B
+  DevBuf gx_wts, gx_wts_in;         // kmg_gkm_cross_w: the laid-out weights of A, then B; the
+                                    // host path's copies of the caller's arrays
   Tuning tune;
   DevBuf cmb_k, cmb_ptrs, cmb_vec, cmb_out, cmb_tmp;  // combination consumers (host path)
   DevBuf sv_mat, sv_vec, sv_info;  // dense learners: factorised system, vectors, info/ipiv
@@ -1839,22 +1841,25 @@ static int gkm_cross_check(const kmg_params *p, int64_t na, int64_t ldc_a, int64
 }
 
 // ... and the bounds of a call whose rows are at most maxlen_a / maxlen_b symbols long
+// (kmg_gkm_cross_w*: a weighted side counts every word up to 255 times, wa / wb = 255, else 1)
 static int gkm_cross_bounds(const kmg_params *p, const GkmWeights &wt, int maxlen_a, int64_t na,
-                            int maxlen_b, int64_t nb, int32_t dt) {
+                            int maxlen_b, int64_t nb, int32_t dt, int wa = 1, int wb = 1) {
   const int l = p->k;
   const int pa = std::max(1, maxlen_a - l + 1), pb = std::max(1, maxlen_b - l + 1);
   const double two53 = 9007199254740992.0, h0 = (double)wt.h[0];
   // every raw value is an exact integer in float64 (and in int32 where that is the output);
   // both strands count twice the pairs, in the block and in the diagonals
   const double ns = p->strands == 2 ? 2.0 : 1.0;
-  const double top = ns * (double)pa * (double)pb * h0;
-  const double dtop = ns * (double)std::max(pa, pb) * (double)std::max(pa, pb) * h0;
+  const double ta = (double)wa * (double)pa, tb = (double)wb * (double)pb;
+  const double top = ns * ta * tb * h0;
+  const double dtop = ns * std::max(ta, tb) * std::max(ta, tb) * h0;
+  const char *wn = wa > 1 || wb > 1 ? ", weights up to 255" : "";
   if (top >= two53 || (p->normalize && dtop >= two53))
-    return fail(KMG_EUNSUPPORTED, "gkm cross: %d x %d words a pair (%d strand%s) can reach 2^53", pa,
-                pb, (int)ns, ns > 1 ? "s" : "");
+    return fail(KMG_EUNSUPPORTED, "gkm cross: %d x %d words a pair (%d strand%s%s) can reach 2^53",
+                pa, pb, (int)ns, ns > 1 ? "s" : "", wn);
   if (dt == KMG_I32 && top >= 2147483648.0)
-    return fail(KMG_EINVAL, "gkm cross: %d x %d words a pair (%d strand%s) can pass int32; use a "
-                "floating dtype", pa, pb, (int)ns, ns > 1 ? "s" : "");
+    return fail(KMG_EINVAL, "gkm cross: %d x %d words a pair (%d strand%s%s) can pass int32; use a "
+                "floating dtype", pa, pb, (int)ns, ns > 1 ? "s" : "", wn);
   const int nba = gkmx_blocks(pa), nbb = gkmx_blocks(pb);
   const int64_t limit = KMG_GKM_MAX_TILES * 8;  // rows a launch grid reaches, words an extract
   if (na >= limit || nb >= limit || (double)na * nba * 32 >= (double)limit * 32 ||
@@ -1870,7 +1875,9 @@ static int gkm_cross_bounds(const kmg_params *p, const GkmWeights &wt, int maxle
 static int gkm_cross_device(kmg_ctx *c, const kmg_params *p, const GkmWeights &wt,
                             const uint8_t *d_ca, const int32_t *d_la, int maxlen_a, int64_t na,
                             int64_t ldc_a, const uint8_t *d_cb, const int32_t *d_lb, int maxlen_b,
-                            int64_t nb, int64_t ldc_b, int32_t dt, void *d_out, int64_t ld) {
+                            int64_t nb, int64_t ldc_b, int32_t dt, void *d_out, int64_t ld,
+                            const uint8_t *d_wa = nullptr, int64_t ldw_a = 0,
+                            const uint8_t *d_wb = nullptr, int64_t ldw_b = 0) {
   c->last_call_first = (int)c->ev_log.size();
   const int l = p->k;
   const bool rc = p->strands == 2;
@@ -1883,12 +1890,20 @@ static int gkm_cross_device(kmg_ctx *c, const kmg_params *p, const GkmWeights &w
   KMG_TRY(c->gx_words_b.ensure(sizeof(uint32_t) * (size_t)nb * nbb * 32));
   KMG_TRY(c->gx_bits.ensure(sizeof(uint32_t) * (size_t)(na * nba + nb * nbb)));
   uint32_t *bits_a = c->gx_bits.as<uint32_t>(), *bits_b = bits_a + na * nba;
-  const GkmxSide A{c->kmers.as<uint32_t>(), bits_a, na, nba};
-  const GkmxSide B{c->gx_words_b.as<uint32_t>(), bits_b, nb, nbb};
+  GkmxSide A{c->kmers.as<uint32_t>(), bits_a, na, nba};
+  GkmxSide B{c->gx_words_b.as<uint32_t>(), bits_b, nb, nbb};
+  if (d_wa || d_wb) {  // a byte a word slot beside the words: A's, then B's
+    const size_t sz_a = d_wa ? (size_t)na * nba * 32 : 0, sz_b = d_wb ? (size_t)nb * nbb * 32 : 0;
+    KMG_TRY(c->gx_wts.ensure(sz_a + sz_b));
+    if (d_wa) A.wts = c->gx_wts.as<uint8_t>();
+    if (d_wb) B.wts = c->gx_wts.as<uint8_t>() + sz_a;
+  }
   struct Side {
     const uint8_t *codes; const int32_t *lens; int64_t n, ldc; int pmax; uint32_t *words, *bits;
-  } sides[2] = {{d_ca, d_la, na, ldc_a, pa, c->kmers.as<uint32_t>(), bits_a},
-                {d_cb, d_lb, nb, ldc_b, pb, c->gx_words_b.as<uint32_t>(), bits_b}};
+    const uint8_t *w; int64_t ldw; const uint8_t *wts;
+  } sides[2] = {{d_ca, d_la, na, ldc_a, pa, c->kmers.as<uint32_t>(), bits_a, d_wa, ldw_a, A.wts},
+                {d_cb, d_lb, nb, ldc_b, pb, c->gx_words_b.as<uint32_t>(), bits_b, d_wb, ldw_b,
+                 B.wts}};
   for (const Side &q : sides) {  // one record buffer: the stream orders B's pack behind A's extract
     const Packed pk{c->packed.as<uint32_t>(), (int64_t)(packed_cw(q.ldc) + packed_mw(q.ldc)),
                     packed_cw(q.ldc)};
@@ -1898,6 +1913,8 @@ static int gkm_cross_device(kmg_ctx *c, const kmg_params *p, const GkmWeights &w
     }
     StageTimer t(c, ST_EXTRACT);
     KMG_HIP(launch_gkmx_extract(pk, q.n, l, q.pmax, q.words, q.bits, c->stream));
+    if (q.w)
+      KMG_HIP(launch_gkmx_weights(q.w, q.ldw, q.lens, q.n, l, q.pmax, (uint8_t *)q.wts, c->stream));
   }
   OutSpec o{d_out, ld, dt, 0, nullptr, nullptr};
   const double *sa = nullptr, *sb = nullptr;
@@ -1916,28 +1933,64 @@ static int gkm_cross_device(kmg_ctx *c, const kmg_params *p, const GkmWeights &w
   return KMG_OK;
 }
 
-int kmg_gkm_cross_device(kmg_ctx *c, const kmg_params *p, const uint8_t *d_codes_a,
-                         const int32_t *d_lens_a, int64_t na, int64_t ldc_a,
-                         const uint8_t *d_codes_b, const int32_t *d_lens_b, int64_t nb,
-                         int64_t ldc_b, int32_t out_dtype, void *d_out, int64_t ld_out) {
+// kmg_gkm_cross_w*: ldw holds the weights of the longest row's words (a side without weights
+// passes); checked with the bounds, before anything is allocated or launched
+static int gkm_cross_ldw(const kmg_params *p, const uint8_t *w, int64_t ldw, int maxlen, char side) {
+  const int words = std::max(0, maxlen - p->k + 1);
+  if (w && ldw < words)
+    return fail(KMG_EINVAL, "gkm cross: ldw_%c = %lld is less than the %d words of the longest row",
+                side, (long long)ldw, words);
+  return KMG_OK;
+}
+
+static int gkm_cross_device_entry(kmg_ctx *c, const kmg_params *p, const uint8_t *d_codes_a,
+                                  const int32_t *d_lens_a, int64_t na, int64_t ldc_a,
+                                  const uint8_t *d_wa, int64_t ldw_a, const uint8_t *d_codes_b,
+                                  const int32_t *d_lens_b, int64_t nb, int64_t ldc_b,
+                                  const uint8_t *d_wb, int64_t ldw_b, int32_t out_dtype,
+                                  void *d_out, int64_t ld_out) {
   if (!c) return fail(KMG_EINVAL, "ctx is NULL");
   std::lock_guard<std::mutex> lk(c->mu);
   GkmWeights wt{};
   KMG_TRY(gkm_cross_check(p, na, ldc_a, nb, ldc_b, out_dtype, wt));
   // (device rows: the lengths are device data, so ldc bounds them, as in kmg_gram_device)
-  KMG_TRY(gkm_cross_bounds(p, wt, (int)ldc_a, na, (int)ldc_b, nb, out_dtype));
+  KMG_TRY(gkm_cross_bounds(p, wt, (int)ldc_a, na, (int)ldc_b, nb, out_dtype, d_wa ? 255 : 1,
+                           d_wb ? 255 : 1));
+  KMG_TRY(gkm_cross_ldw(p, d_wa, ldw_a, (int)ldc_a, 'a'));
+  KMG_TRY(gkm_cross_ldw(p, d_wb, ldw_b, (int)ldc_b, 'b'));
   if (na == 0 || nb == 0) return KMG_OK;
   if (!d_codes_a || !d_lens_a || !d_codes_b || !d_lens_b || !d_out)
     return fail(KMG_EINVAL, "NULL buffer");
   if (ld_out < nb) return fail(KMG_EINVAL, "ld_out < nb");
   KMG_HIP(hipSetDevice(c->device));
   return gkm_cross_device(c, p, wt, d_codes_a, d_lens_a, (int)ldc_a, na, ldc_a, d_codes_b, d_lens_b,
-                          (int)ldc_b, nb, ldc_b, out_dtype, d_out, ld_out);
+                          (int)ldc_b, nb, ldc_b, out_dtype, d_out, ld_out, d_wa, ldw_a, d_wb, ldw_b);
 }
 
-int kmg_gkm_cross(kmg_ctx *c, const kmg_params *p, const uint8_t *codes_a, const int32_t *lens_a,
-                  int64_t na, int64_t ldc_a, const uint8_t *codes_b, const int32_t *lens_b,
-                  int64_t nb, int64_t ldc_b, int32_t out_dtype, void *out, int64_t ld_out) {
+int kmg_gkm_cross_device(kmg_ctx *c, const kmg_params *p, const uint8_t *d_codes_a,
+                         const int32_t *d_lens_a, int64_t na, int64_t ldc_a,
+                         const uint8_t *d_codes_b, const int32_t *d_lens_b, int64_t nb,
+                         int64_t ldc_b, int32_t out_dtype, void *d_out, int64_t ld_out) {
+  return gkm_cross_device_entry(c, p, d_codes_a, d_lens_a, na, ldc_a, nullptr, 0, d_codes_b,
+                                d_lens_b, nb, ldc_b, nullptr, 0, out_dtype, d_out, ld_out);
+}
+
+int kmg_gkm_cross_w_device(kmg_ctx *c, const kmg_params *p, const uint8_t *d_codes_a,
+                           const int32_t *d_lens_a, int64_t na, int64_t ldc_a,
+                           const uint8_t *d_wts_a, int64_t ldw_a, const uint8_t *d_codes_b,
+                           const int32_t *d_lens_b, int64_t nb, int64_t ldc_b,
+                           const uint8_t *d_wts_b, int64_t ldw_b, int32_t out_dtype, void *d_out,
+                           int64_t ld_out) {
+  return gkm_cross_device_entry(c, p, d_codes_a, d_lens_a, na, ldc_a, d_wts_a, ldw_a, d_codes_b,
+                                d_lens_b, nb, ldc_b, d_wts_b, ldw_b, out_dtype, d_out, ld_out);
+}
+
+static int gkm_cross_host_entry(kmg_ctx *c, const kmg_params *p, const uint8_t *codes_a,
+                                const int32_t *lens_a, int64_t na, int64_t ldc_a,
+                                const uint8_t *wts_a, int64_t ldw_a, const uint8_t *codes_b,
+                                const int32_t *lens_b, int64_t nb, int64_t ldc_b,
+                                const uint8_t *wts_b, int64_t ldw_b, int32_t out_dtype, void *out,
+                                int64_t ld_out) {
   if (!c) return fail(KMG_EINVAL, "ctx is NULL");
   std::lock_guard<std::mutex> lk(c->mu);
   GkmWeights wt{};
@@ -1956,7 +2009,12 @@ int kmg_gkm_cross(kmg_ctx *c, const kmg_params *p, const uint8_t *codes_a, const
       maxlen[s] = std::max(maxlen[s], (int)lens[i]);
     }
   }
-  KMG_TRY(gkm_cross_bounds(p, wt, maxlen[0], na, maxlen[1], nb, out_dtype));
+  KMG_TRY(gkm_cross_bounds(p, wt, maxlen[0], na, maxlen[1], nb, out_dtype, wts_a ? 255 : 1,
+                           wts_b ? 255 : 1));
+  if (!empty) {
+    KMG_TRY(gkm_cross_ldw(p, wts_a, ldw_a, maxlen[0], 'a'));
+    KMG_TRY(gkm_cross_ldw(p, wts_b, ldw_b, maxlen[1], 'b'));
+  }
   if (empty) return KMG_OK;
   KMG_HIP(hipSetDevice(c->device));
   const size_t esz = dtype_size(out_dtype);
@@ -1971,12 +2029,44 @@ int kmg_gkm_cross(kmg_ctx *c, const kmg_params *p, const uint8_t *codes_a, const
   KMG_HIP(hipMemcpyAsync(d_cb, codes_b, (size_t)nb * ldc_b, hipMemcpyHostToDevice, c->stream));
   KMG_HIP(hipMemcpyAsync(d_la, lens_a, sizeof(int32_t) * na, hipMemcpyHostToDevice, c->stream));
   KMG_HIP(hipMemcpyAsync(d_lb, lens_b, sizeof(int32_t) * nb, hipMemcpyHostToDevice, c->stream));
+  const uint8_t *d_wa = nullptr, *d_wb = nullptr;
+  if (wts_a || wts_b) {  // the caller's arrays as they are; the device lays them out
+    const size_t sz_a = wts_a ? (((size_t)na * ldw_a + 15) & ~(size_t)15) : 0;
+    const size_t sz_b = wts_b ? (size_t)nb * ldw_b : 0;
+    KMG_TRY(c->gx_wts_in.ensure(std::max<size_t>(sz_a + sz_b, 16)));
+    uint8_t *d_w = c->gx_wts_in.as<uint8_t>();
+    if (wts_a && na * ldw_a > 0) {
+      KMG_HIP(hipMemcpyAsync(d_w, wts_a, (size_t)na * ldw_a, hipMemcpyHostToDevice, c->stream));
+    }
+    if (wts_b && nb * ldw_b > 0) {
+      KMG_HIP(hipMemcpyAsync(d_w + sz_a, wts_b, (size_t)nb * ldw_b, hipMemcpyHostToDevice,
+                             c->stream));
+    }
+    if (wts_a) d_wa = d_w;
+    if (wts_b) d_wb = d_w + sz_a;
+  }
   KMG_TRY(gkm_cross_device(c, p, wt, d_ca, d_la, maxlen[0], na, ldc_a, d_cb, d_lb, maxlen[1], nb,
-                           ldc_b, out_dtype, c->h_out.p, ldd));
+                           ldc_b, out_dtype, c->h_out.p, ldd, d_wa, ldw_a, d_wb, ldw_b));
   KMG_HIP(hipMemcpy2DAsync(out, (size_t)ld_out * esz, c->h_out.p, (size_t)ldd * esz,
                            (size_t)nb * esz, (size_t)na, hipMemcpyDeviceToHost, c->stream));
   KMG_HIP(hipStreamSynchronize(c->stream));
   return KMG_OK;
+}
+
+int kmg_gkm_cross(kmg_ctx *c, const kmg_params *p, const uint8_t *codes_a, const int32_t *lens_a,
+                  int64_t na, int64_t ldc_a, const uint8_t *codes_b, const int32_t *lens_b,
+                  int64_t nb, int64_t ldc_b, int32_t out_dtype, void *out, int64_t ld_out) {
+  return gkm_cross_host_entry(c, p, codes_a, lens_a, na, ldc_a, nullptr, 0, codes_b, lens_b, nb,
+                              ldc_b, nullptr, 0, out_dtype, out, ld_out);
+}
+
+int kmg_gkm_cross_w(kmg_ctx *c, const kmg_params *p, const uint8_t *codes_a, const int32_t *lens_a,
+                    int64_t na, int64_t ldc_a, const uint8_t *wts_a, int64_t ldw_a,
+                    const uint8_t *codes_b, const int32_t *lens_b, int64_t nb, int64_t ldc_b,
+                    const uint8_t *wts_b, int64_t ldw_b, int32_t out_dtype, void *out,
+                    int64_t ld_out) {
+  return gkm_cross_host_entry(c, p, codes_a, lens_a, na, ldc_a, wts_a, ldw_a, codes_b, lens_b, nb,
+                              ldc_b, wts_b, ldw_b, out_dtype, out, ld_out);
 }
 
 int kmg_gram_device_cols(kmg_ctx *c, const kmg_params *p, const uint8_t *d_codes,

@@ -19,7 +19,7 @@
 //
 // gkmx_extract_kernel   packed records -> words [n][32 nblk] (0 where invalid) and validity
 //                       bits [n][nblk], nblk = ceil(pmax / 32) blocks of 32 words a row.
-// gram_gkmx_kernel<DIAG, TWO, RC>   one 256-thread workgroup a tile of 16 rows x 8 columns.
+// gram_gkmx_kernel<DIAG, TWO, RC, WT>   one 256-thread workgroup a tile of 16 rows x 8 columns.
 //   LDS     one chunk of 8 blocks (256 words) of every tile row and column, 4 B a word:
 //           16 KB + 8 KB, their validity words (768 B), hm (80 B) and the int64 result tile
 //           (1 KB): 26 KB whatever pmax is.  The chunk loops (A chunks outside, B chunks
@@ -63,6 +63,31 @@
 //           other set's MFMA is in flight.  Both sets' lookups add into one int32 partial (at
 //           most 32 adds of <= 12870) before the flush into the lane's int64: the flush rule
 //           holds with twice the count.
+//   WT      position weights (kmg_gkm_cross_w*, LS-GKM's wgkm): every word carries a weight 0..255
+//           that depends on where it starts in its row, and a word pair counts with the product,
+//             Kw(x, y) = sum_{a, b} u_x[a] v_y[b] h[ham(x_a, y_b)]   (RC: ... + h[ham(x_a, rc(y_b))])
+//           h is not linear in the match count, so the weights cannot go into the one-hot
+//           operands: they are applied to the lookups.  GkmxSide.wts holds one byte a word slot
+//           in the layout of the words (gkmx_weights_kernel lays the caller's [n][ldw] out); a
+//           side without weights (nullptr) is staged as all ones.  The staged chunks bring their
+//           weights along (256 B a row and a column), one 16-byte load a thread in the same
+//           chunk loops, no extra barrier.
+//           In an MFMA result a lane's 16 entries share the B word (lane & 31) and belong to the
+//           A words 8 (e / 4) + 4 half + e % 4, so per row of a sweep the lane keeps 16 int32
+//           partials T[e] += vB * hm[...] (v_mad_u32_u24; vB one ds_read_u8 a B block; under RC
+//           the two sets' lookups are two such multiply-adds with the same vB).  After the
+//           column's staged B blocks (at most 8) the partials are flushed, S += sum_e uA[e] T[e]
+//           (v_mad_u64_u32; uA the bytes of four aligned dwords of the staged weight row, read
+//           once an A block), and start again from 0.  Bounds: T <= 8 * 2 * 255 * 12870 < 2^26;
+//           uA * T < 2^34, hence the 64-bit flush; the pair's total is exact in int64 (the API
+//           bounds it below 2^53).  An invalid or absent word looks up hm[0] = 0 whatever its
+//           weight is, and weight 0 excludes a word.  T costs 16 VGPRs a row, so a WT tile is
+//           GX_WTR = 8 rows x 8 columns and a wave owns two rows where the unweighted one owns
+//           four: 32 VGPRs of T against 32 fewer of the int64 sums and 16 fewer of A operands,
+//           which keeps every instantiation at two waves a SIMD without scratch (the kernel asks
+//           for it in its launch bounds).  LDS: 8 KB + 8 KB of words, 2 KB + 2 KB of weights,
+//           validity, hm, result: 22 KB.  DIAG: sqrt(Kw(x, x)), both sides staged with x's
+//           weights.
 #include "kmg_internal.h"
 
 namespace kmg {
@@ -76,6 +101,7 @@ constexpr int GX_TR = 16;           // tile rows
 constexpr int GX_TC = 8;            // tile columns (and the rows of a DIAG tile)
 constexpr int GX_CB = 8;            // 32-word blocks a staged chunk
 constexpr int GX_CW = 32 * GX_CB;   // words a staged chunk
+constexpr int GX_WTR = 8;           // tile rows of the weighted kernel (WT)
 
 // code and validity of window a of a packed record (pk_window with the validity kept apart)
 __device__ __forceinline__ uint32_t gx_window(const uint32_t *rec, int cw, int a, int l, bool &ok) {
@@ -105,6 +131,25 @@ __global__ __launch_bounds__(256) void gkmx_extract_kernel(Packed pk, int64_t n,
   if (!in) return;
   words[t] = ok ? code : 0u;
   if ((threadIdx.x & 31) == 0) bits[t >> 5] = (uint32_t)(b >> (threadIdx.x & 32));
+}
+
+// the caller's weights [n][ldw] -> one byte a word slot, [n][32 nblk], 0 past the row's last
+// word; one thread four slots
+__global__ __launch_bounds__(256) void gkmx_weights_kernel(const uint8_t *__restrict__ w,
+                                                           int64_t ldw,
+                                                           const int32_t *__restrict__ lens,
+                                                           int64_t n, int l, int nblk,
+                                                           uint32_t *__restrict__ out) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x, q = (int64_t)nblk * 8;
+  if (t >= n * q) return;
+  const int64_t j = t / q;
+  const int a = (int)(t - j * q) * 4;
+  const int64_t np = min((int64_t)lens[j] - l + 1, ldw);
+  uint32_t v = 0u;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (a + i < np) v |= (uint32_t)w[j * ldw + a + i] << (8 * i);
+  out[t] = v;
 }
 
 template <bool TWO>
@@ -201,21 +246,81 @@ __device__ __forceinline__ void gx_sweep(const GxLane<TWO> &L, const v4i (&a0)[N
   }
 }
 
-template <bool DIAG, bool TWO, bool RC>
-__global__ __launch_bounds__(256) void gram_gkmx_kernel(GkmxSide A, GkmxSide B, int l, int64_t row0,
-                                                        int64_t rows, int64_t tiles_c,
-                                                        GkmWeights wt, OutSpec o,
-                                                        const double *__restrict__ sa,
-                                                        const double *__restrict__ sb,
-                                                        double *__restrict__ dsq_out) {
-  __shared__ __align__(16) uint32_t wa[GX_TR][GX_CW];
+// WT: the same sweep with the lookups weighted.  ua[r]: the four dwords of row r's staged
+// weights that hold the lane's 16 A words; ucol: the column's staged weight bytes.  T <= 8 * 2
+// * 255 * 12870 < 2^26 and uA * T < 2^34: the flush is a 64-bit multiply-add.
+template <int NR, bool TWO, bool RC>
+__device__ __forceinline__ void gx_sweep_w(const GxLane<TWO> &L, const v4i (&a0)[NR],
+                                           const v4i (&a1)[NR], const uint32_t (&ua)[NR][4],
+                                           const uint32_t *wcol, const uint32_t *vcol,
+                                           const uint8_t *ucol, int nbb, const int32_t *hm,
+                                           int64_t *S) {
+  uint32_t T[NR][16];
+#pragma unroll
+  for (int r = 0; r < NR; ++r)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) T[r][e] = 0u;
+  auto add = [&](uint32_t (&t)[16], const v16i &acc, uint32_t vB) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e)
+      t[e] += __umul24(vB, (uint32_t) * (const int32_t *)((const char *)hm + acc[e]));
+  };
+  for (int bb = 0; bb < nbb; ++bb) {
+    const uint32_t vw = __builtin_amdgcn_readfirstlane(vcol[bb]);
+    if (vw == 0u) continue;
+    v4i b0, b1;
+    const uint32_t w = wcol[bb * 32 + L.lr];
+    const uint32_t vB = ucol[bb * 32 + L.lr];
+    gx_expand<TWO>(L, w, b0, b1);
+    if (vw != 0xFFFFFFFFu) gx_mask<TWO>(L, vw, b0, b1);
+    if constexpr (!RC) {
+#pragma unroll
+      for (int r = 0; r < NR; ++r) add(T[r], gx_mfma<TWO>(a0[r], a1[r], b0, b1), vB);
+    } else {
+      v4i c0, c1;
+      gx_expand_left<TWO>(L, gx_pairrev32(w) ^ (0xFFFFFFFFu << L.lsh), c0, c1);
+      if (vw != 0xFFFFFFFFu) gx_mask<TWO>(L, vw, c0, c1);
+      v16i f = gx_mfma<TWO>(a0[0], a1[0], b0, b1);
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+        const v16i g = gx_mfma<TWO>(a0[r], a1[r], c0, c1);  // in flight under f's lookups
+        add(T[r], f, vB);
+        if (r + 1 < NR) f = gx_mfma<TWO>(a0[r + 1], a1[r + 1], b0, b1);  // ... under g's
+        add(T[r], g, vB);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < NR; ++r) {
+    uint64_t acc = (uint64_t)S[r];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      uint32_t u = ua[r][q];
+      asm volatile("" : "+v"(u));  // unpack the bytes here, not once for all eight columns
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        acc += (uint64_t)((u >> (8 * i)) & 0xFFu) * (uint64_t)T[r][4 * q + i];
+    }
+    S[r] = (int64_t)acc;
+  }
+}
+
+template <bool DIAG, bool TWO, bool RC, bool WT>
+__global__ __launch_bounds__(256, WT ? 2 : 1) void gram_gkmx_kernel(
+    GkmxSide A, GkmxSide B, int l, int64_t row0, int64_t rows, int64_t tiles_c, GkmWeights wt,
+    OutSpec o, const double *__restrict__ sa, const double *__restrict__ sb,
+    double *__restrict__ dsq_out) {
+  constexpr int TRL = WT ? GX_WTR : GX_TR;            // tile rows the LDS holds
+  __shared__ __align__(16) uint32_t wa[TRL][GX_CW];
   __shared__ __align__(16) uint32_t wb[GX_TC][GX_CW];
-  __shared__ uint32_t va[GX_TR][GX_CB], vb[GX_TC][GX_CB];
+  __shared__ uint32_t va[TRL][GX_CB], vb[GX_TC][GX_CB];
+  __shared__ __align__(16) uint32_t ua[WT ? GX_WTR : 1][GX_CW / 4];  // WT: a weight byte a word
+  __shared__ __align__(16) uint32_t ub[WT ? GX_TC : 1][GX_CW / 4];
   __shared__ int32_t hm[20];
   __shared__ int64_t res[GX_TR][GX_TC];
-  constexpr int TRR = DIAG ? GX_TC : GX_TR;  // rows a tile
-  constexpr int NRW = DIAG ? 1 : 4;          // rows of one sweep
-  constexpr int NCW = DIAG ? 2 : GX_TC;      // sweeps' sums a wave
+  constexpr int TRR = DIAG ? GX_TC : TRL;             // rows a tile
+  constexpr int NRW = DIAG ? 1 : TRR / 4;             // rows of one sweep
+  constexpr int NCW = DIAG ? 2 : GX_TC;               // sweeps' sums a wave
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int64_t i0, j0;
@@ -225,9 +330,9 @@ __global__ __launch_bounds__(256) void gram_gkmx_kernel(GkmxSide A, GkmxSide B, 
     nr = nc = (int)min((int64_t)GX_TC, A.n - i0);
   } else {
     const int64_t tr = (int64_t)blockIdx.x / tiles_c, tc = (int64_t)blockIdx.x - tr * tiles_c;
-    i0 = row0 + tr * GX_TR;
+    i0 = row0 + tr * TRR;
     j0 = tc * GX_TC;
-    nr = (int)min((int64_t)GX_TR, row0 + rows - i0);
+    nr = (int)min((int64_t)TRR, row0 + rows - i0);
     nc = (int)min((int64_t)GX_TC, B.n - j0);
   }
 
@@ -268,6 +373,19 @@ __global__ __launch_bounds__(256) void gram_gkmx_kernel(GkmxSide A, GkmxSide B, 
           const int r = tid / GX_CB, blk = ca * GX_CB + tid % GX_CB;
           va[r][tid % GX_CB] = (r < nr && blk < A.nblk) ? A.bits[(i0 + r) * A.nblk + blk] : 0u;
         }
+        if constexpr (WT) {
+          if (tid < TRR * (GX_CW / 16)) {
+            const int r = tid / (GX_CW / 16), q16 = (tid % (GX_CW / 16)) * 16;
+            const int blk = ca * GX_CB + (q16 >> 5);
+            uint4 v = make_uint4(0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u);
+            if (A.wts) {
+              v = make_uint4(0u, 0u, 0u, 0u);
+              if (r < nr && blk < A.nblk)
+                v = *(const uint4 *)(A.wts + ((i0 + r) * A.nblk + blk) * 32 + (q16 & 31));
+            }
+            *(uint4 *)&ua[r][q16 / 4] = v;
+          }
+        }
       }
       for (int t = tid; t < GX_TC * (GX_CW / 4); t += 256) {
         const int r = t / (GX_CW / 4), q4 = (t % (GX_CW / 4)) * 4, blk = cb * GX_CB + (q4 >> 5);
@@ -279,6 +397,19 @@ __global__ __launch_bounds__(256) void gram_gkmx_kernel(GkmxSide A, GkmxSide B, 
       if (tid < GX_TC * GX_CB) {
         const int r = tid / GX_CB, blk = cb * GX_CB + tid % GX_CB;
         vb[r][tid % GX_CB] = (r < nc && blk < B.nblk) ? B.bits[(j0 + r) * B.nblk + blk] : 0u;
+      }
+      if constexpr (WT) {
+        if (tid >= 128) {  // (the first two waves have staged the validity words)
+          const int t = tid - 128, r = t / (GX_CW / 16), q16 = (t % (GX_CW / 16)) * 16;
+          const int blk = cb * GX_CB + (q16 >> 5);
+          uint4 v = make_uint4(0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u);
+          if (B.wts) {
+            v = make_uint4(0u, 0u, 0u, 0u);
+            if (r < nc && blk < B.nblk)
+              v = *(const uint4 *)(B.wts + ((j0 + r) * B.nblk + blk) * 32 + (q16 & 31));
+          }
+          *(uint4 *)&ub[r][q16 / 4] = v;
+        }
       }
       __syncthreads();
 
@@ -294,7 +425,39 @@ __global__ __launch_bounds__(256) void gram_gkmx_kernel(GkmxSide A, GkmxSide B, 
             v4i a0[1], a1[1];
             gx_expand<TWO>(L, wa[r][ab * 32 + L.lr], a0[0], a1[0]);
             gx_mask<TWO>(L, vw, a0[0], a1[0]);
-            gx_sweep<1, TWO, RC>(L, a0, a1, wb[r], vb[r], nbb, hm, S[rr]);
+            if constexpr (WT) {
+              uint32_t u[1][4];
+#pragma unroll
+              for (int q = 0; q < 4; ++q) u[0][q] = ua[r][ab * 8 + 2 * q + half];
+              gx_sweep_w<1, TWO, RC>(L, a0, a1, u, wb[r], vb[r], (const uint8_t *)ub[r], nbb, hm,
+                                     S[rr]);
+            } else {
+              gx_sweep<1, TWO, RC>(L, a0, a1, wb[r], vb[r], nbb, hm, S[rr]);
+            }
+          }
+        }
+      } else if constexpr (WT) {
+        const int rb = NRW * wave;
+        if (rb < nr) {  // wave-uniform
+          for (int ab = 0; ab < nba; ++ab) {
+            v4i a0[NRW], a1[NRW];
+            uint32_t u[NRW][4];
+            uint32_t any = 0u;
+#pragma unroll
+            for (int r = 0; r < NRW; ++r) {
+              const uint32_t vw = va[rb + r][ab];
+              any |= vw;
+              gx_expand<TWO>(L, wa[rb + r][ab * 32 + L.lr], a0[r], a1[r]);
+              gx_mask<TWO>(L, vw, a0[r], a1[r]);
+#pragma unroll
+              for (int q = 0; q < 4; ++q) u[r][q] = ua[rb + r][ab * 8 + 2 * q + half];
+            }
+            if (__builtin_amdgcn_readfirstlane(any) == 0u) continue;
+#pragma unroll
+            for (int c = 0; c < GX_TC; ++c)
+              if (c < nc)
+                gx_sweep_w<NRW, TWO, RC>(L, a0, a1, u, wb[c], vb[c], (const uint8_t *)ub[c], nbb,
+                                         hm, S[c]);
           }
         }
       } else {
@@ -330,7 +493,7 @@ __global__ __launch_bounds__(256) void gram_gkmx_kernel(GkmxSide A, GkmxSide B, 
       for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
       if (lane == 0) {
         if constexpr (DIAG) res[2 * wave + c][0] = v;
-        else res[4 * wave + r][c] = v;
+        else res[NRW * wave + r][c] = v;
       }
     }
   __syncthreads();
@@ -353,7 +516,30 @@ __global__ __launch_bounds__(256) void gram_gkmx_kernel(GkmxSide A, GkmxSide B, 
   }
 }
 
+// the instantiation of a launch: two MFMA steps (l > 8), both strands, position weights
+template <bool DIAG>
+auto gx_kernel(bool two, bool rc, bool wt) {
+  decltype(&gram_gkmx_kernel<DIAG, false, false, false>) k[8] = {
+      gram_gkmx_kernel<DIAG, false, false, false>, gram_gkmx_kernel<DIAG, false, false, true>,
+      gram_gkmx_kernel<DIAG, false, true, false>,  gram_gkmx_kernel<DIAG, false, true, true>,
+      gram_gkmx_kernel<DIAG, true, false, false>,  gram_gkmx_kernel<DIAG, true, false, true>,
+      gram_gkmx_kernel<DIAG, true, true, false>,   gram_gkmx_kernel<DIAG, true, true, true>};
+  return k[4 * two + 2 * rc + wt];
+}
+
 }  // namespace
+
+hipError_t launch_gkmx_weights(const uint8_t *w, int64_t ldw, const int32_t *lens, int64_t n, int l,
+                               int pmax, uint8_t *out, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (pmax < 1 || l < 1 || l > 16 || ldw < 0 || !w || !lens || !out) return hipErrorInvalidValue;
+  const int nblk = gkmx_blocks(pmax);
+  const int64_t blocks = (n * nblk * 8 + 255) / 256;
+  if (blocks >= KMG_GKM_MAX_TILES) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gkmx_weights_kernel, dim3((unsigned)blocks), dim3(256), 0, s, w, ldw, lens, n,
+                     l, nblk, (uint32_t *)out);
+  return hipGetLastError();
+}
 
 hipError_t launch_gkmx_extract(const Packed &pk, int64_t n, int l, int pmax, uint32_t *words,
                                uint32_t *bits, hipStream_t s) {
@@ -375,14 +561,14 @@ hipError_t launch_gram_gkmx(const GkmxSide &A, const GkmxSide &B, int l, bool rc
   if (o.normalize && (!sa || !sb)) return hipErrorInvalidValue;
   const int64_t tiles_c = (B.n + GX_TC - 1) / GX_TC;
   if (tiles_c >= KMG_GKM_MAX_TILES) return hipErrorInvalidValue;  // AQL grid size is 32-bit
-  const int64_t max_rows = (KMG_GKM_MAX_TILES - 1) / tiles_c * GX_TR;
+  const bool wts = A.wts || B.wts;
+  const int tr = wts ? GX_WTR : GX_TR;
+  const int64_t max_rows = (KMG_GKM_MAX_TILES - 1) / tiles_c * tr;
   const size_t esz = o.dtype == KMG_F64 ? 8 : 4;
-  auto kern = gram_gkmx_kernel<false, false, false>;
-  if (l > 8) kern = rc ? gram_gkmx_kernel<false, true, true> : gram_gkmx_kernel<false, true, false>;
-  else if (rc) kern = gram_gkmx_kernel<false, false, true>;
+  const auto kern = gx_kernel<false>(l > 8, rc, wts);
   for (int64_t r0 = 0; r0 < A.n; r0 += max_rows) {
     const int64_t rows = A.n - r0 < max_rows ? A.n - r0 : max_rows;
-    const dim3 grid((unsigned)((rows + GX_TR - 1) / GX_TR * tiles_c));
+    const dim3 grid((unsigned)((rows + tr - 1) / tr * tiles_c));
     OutSpec os = o;
     os.out = (char *)o.out + (size_t)r0 * o.ld * esz;
     hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, A, B, l, r0, rows, tiles_c, wt, os, sa, sb,
@@ -400,9 +586,7 @@ hipError_t launch_gkmx_diag(const GkmxSide &A, int l, bool rc, const GkmWeights 
   const int64_t tiles = (A.n + GX_TC - 1) / GX_TC;
   if (tiles >= KMG_GKM_MAX_TILES) return hipErrorInvalidValue;
   const OutSpec o{};
-  auto kern = gram_gkmx_kernel<true, false, false>;
-  if (l > 8) kern = rc ? gram_gkmx_kernel<true, true, true> : gram_gkmx_kernel<true, true, false>;
-  else if (rc) kern = gram_gkmx_kernel<true, false, true>;
+  const auto kern = gx_kernel<true>(l > 8, rc, A.wts != nullptr);
   hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), 0, s, A, A, l, (int64_t)0, A.n,
                      (int64_t)1, wt, o, (const double *)nullptr, (const double *)nullptr, dsq);
   return hipGetLastError();

@@ -299,24 +299,32 @@ hipError_t launch_gkm_diag(const uint32_t *words, int pmax, int l, bool rc, int6
 // ---------------------------------------------------------------- gkm cross (kmg_gkmx.hip)
 // rectangular gkm block Kx[i][j] = sum_{a,b} h[ham(A_i word a, B_j word b)] on int8 MFMA, rows
 // of any length.  One side's words: [n][32 nblk] uint32 (0 where invalid) and validity bits
-// [n][nblk] (bit t of word q: word 32 q + t counts), nblk = gkmx_blocks(pmax)
+// [n][nblk] (bit t of word q: word 32 q + t counts), nblk = gkmx_blocks(pmax).  wts: the words'
+// position weights, one byte a word slot [n][32 nblk] (launch_gkmx_weights), or nullptr: the
+// side is unweighted (every weight 1)
 struct GkmxSide {
   const uint32_t *words;
   const uint32_t *bits;
   int64_t n;
   int nblk;
+  const uint8_t *wts = nullptr;
 };
 inline int gkmx_blocks(int pmax) { return (pmax + 31) / 32; }
 hipError_t launch_gkmx_extract(const Packed &pk, int64_t n, int l, int pmax, uint32_t *words,
                                uint32_t *bits, hipStream_t s);
+// the caller's weights w [n][ldw] (word a of row j at w[j][a]) -> out [n][32 nblk], 0 from the
+// row's word count lens[j] - l + 1 (and from ldw) on
+hipError_t launch_gkmx_weights(const uint8_t *w, int64_t ldw, const int32_t *lens, int64_t n, int l,
+                               int pmax, uint8_t *out, hipStream_t s);
 // all A.n x B.n pairs at o.out (o.out, o.ld, o.dtype, o.normalize are read); normalised:
 // raw / (sa[i] * sb[j]).  Rows are split so every launch stays below KMG_GKM_MAX_TILES tiles.
-// rc: both strands, Kx(A_i, B_j) + Kx(A_i, rc(B_j)), from the same words and bits.
+// rc: both strands, Kx(A_i, B_j) + Kx(A_i, rc(B_j)), from the same words and bits.  With
+// weights on either side: sum_{a,b} u_A[a] v_B[b] h[...] (the WT instantiations).
 hipError_t launch_gram_gkmx(const GkmxSide &A, const GkmxSide &B, int l, bool rc,
                             const GkmWeights &wt, const OutSpec &o, const double *sa,
                             const double *sb, hipStream_t s);
 // dsq[i] = sqrt(K(A_i, A_i)) (rc: of the both-strands K2), from the same kernel over the
-// pairs (i, i)
+// pairs (i, i); A's weights, where it has any, on both sides
 hipError_t launch_gkmx_diag(const GkmxSide &A, int l, bool rc, const GkmWeights &wt, double *dsq,
                             hipStream_t s);
 

@@ -39,7 +39,7 @@ EXPORTS = (
     "kmg_gram_to_host", "kmg_gram_blocks_wire", "kmg_last_plan", "kmg_features",
     "kmg_last_factorisation", "kmg_features_sym", "kmg_gram_device_cols",
     "kmg_scorer_create", "kmg_scorer_score", "kmg_scorer_score_device", "kmg_scorer_destroy",
-    "kmg_gkm_cross", "kmg_gkm_cross_device",
+    "kmg_gkm_cross", "kmg_gkm_cross_device", "kmg_gkm_cross_w", "kmg_gkm_cross_w_device",
 )
 KMG_FEATURES_BCAST = 1
 KMG_FACTOR_CHOLESKY, KMG_FACTOR_LU_ASYMMETRIC, KMG_FACTOR_LU_INDEFINITE = 1, 2, 3
@@ -103,6 +103,10 @@ def load():
                                P, I64], ctypes.c_int),
             "kmg_gkm_cross_device": ([P, ctypes.POINTER(KmgParams), P, P, I64, I64, P, P, I64, I64,
                                       I32, P, I64], ctypes.c_int),
+            "kmg_gkm_cross_w": ([P, ctypes.POINTER(KmgParams), P, P, I64, I64, P, I64, P, P, I64,
+                                 I64, P, I64, I32, P, I64], ctypes.c_int),
+            "kmg_gkm_cross_w_device": ([P, ctypes.POINTER(KmgParams), P, P, I64, I64, P, I64, P, P,
+                                        I64, I64, P, I64, I32, P, I64], ctypes.c_int),
             "kmg_features": ([P, ctypes.POINTER(KmgParams), P, P, I64, I64, P, I64, P, I64],
                              ctypes.c_int),
             "kmg_features_sym": ([P, ctypes.POINTER(KmgParams), P, P, I64, I64, P, I64, I32, P,
@@ -255,18 +259,28 @@ class Context:
                                 out_dtype, ptr(out), n))
         return out
 
-    def gkm_cross(self, params, codes_a, lens_a, codes_b, lens_b, out_dtype=KMG_F64):
+    def gkm_cross(self, params, codes_a, lens_a, codes_b, lens_b, out_dtype=KMG_F64,
+                  weights_a=None, weights_b=None):
         """[na, nb] gapped k-mer block between the rows of A and of B, rows of any length
-        (kmg_gkm_cross; params from ``params.gkm``)."""
+        (kmg_gkm_cross; params from ``params.gkm``).  weights_a / weights_b: uint8 [n, ldw]
+        position weights of a side's words (kmg_gkm_cross_w), None for all ones."""
         codes_a = np.ascontiguousarray(codes_a, dtype=np.uint8)
         codes_b = np.ascontiguousarray(codes_b, dtype=np.uint8)
         lens_a = np.ascontiguousarray(lens_a, dtype=np.int32)
         lens_b = np.ascontiguousarray(lens_b, dtype=np.int32)
         (na, ldc_a), (nb, ldc_b) = codes_a.shape, codes_b.shape
         out = np.empty((na, nb), dtype=DTYPES[out_dtype])
-        check(self.lib.kmg_gkm_cross(self._h, ctypes.byref(params), ptr(codes_a), ptr(lens_a), na,
-                                     ldc_a, ptr(codes_b), ptr(lens_b), nb, ldc_b, out_dtype,
-                                     ptr(out), nb))
+        if weights_a is None and weights_b is None:
+            check(self.lib.kmg_gkm_cross(self._h, ctypes.byref(params), ptr(codes_a), ptr(lens_a),
+                                         na, ldc_a, ptr(codes_b), ptr(lens_b), nb, ldc_b,
+                                         out_dtype, ptr(out), nb))
+            return out
+        wa, wb = (None if w is None else np.ascontiguousarray(w, dtype=np.uint8).reshape(n, -1)
+                  for w, n in ((weights_a, na), (weights_b, nb)))
+        check(self.lib.kmg_gkm_cross_w(
+            self._h, ctypes.byref(params), ptr(codes_a), ptr(lens_a), na, ldc_a, ptr(wa),
+            0 if wa is None else wa.shape[1], ptr(codes_b), ptr(lens_b), nb, ldc_b, ptr(wb),
+            0 if wb is None else wb.shape[1], out_dtype, ptr(out), nb))
         return out
 
     def gkm_cross_device(self, params, d_codes_a, d_lens_a, na, ldc_a, d_codes_b, d_lens_b, nb,
@@ -275,6 +289,13 @@ class Context:
         check(self.lib.kmg_gkm_cross_device(self._h, ctypes.byref(params), d_codes_a, d_lens_a, na,
                                             ldc_a, d_codes_b, d_lens_b, nb, ldc_b, out_dtype,
                                             d_out, ld))
+
+    def gkm_cross_w_device(self, params, d_codes_a, d_lens_a, na, ldc_a, d_wts_a, ldw_a,
+                           d_codes_b, d_lens_b, nb, ldc_b, d_wts_b, ldw_b, out_dtype, d_out, ld):
+        """The weighted block on device pointers (kmg_gkm_cross_w_device; d_wts_x None: ones)."""
+        check(self.lib.kmg_gkm_cross_w_device(
+            self._h, ctypes.byref(params), d_codes_a, d_lens_a, na, ldc_a, d_wts_a, ldw_a,
+            d_codes_b, d_lens_b, nb, ldc_b, d_wts_b, ldw_b, out_dtype, d_out, ld))
 
     def features(self, params, codes, lens, cols):
         """float64 [n, len(cols)] feature rows (kmg_features): column j scores the k-mer code

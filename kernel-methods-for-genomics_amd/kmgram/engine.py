@@ -187,7 +187,9 @@ class GramEngine:
         sequence without a valid word (its K_ii would be 0) raises ValueError.
         both_strands=True counts a word together with its reverse complement, as gkm-SVM does
         by default: K(x, y) + K(x, rc(y)), symmetric, the diagonals of normalize_K included.
-        It needs l <= 15 here (ValueError otherwise); ``gkm_cross`` serves l = 16."""
+        It needs l <= 15 here (ValueError otherwise); ``gkm_cross`` serves l = 16.  The square
+        path takes no position weights: ``gkm_cross(s, s, weights_a=w, weights_b=w)`` is the
+        weighted square Gram."""
         p = P.gkm(l, k, d, normalize, both_strands)
         if both_strands and int(l) == 16:
             raise ValueError("gkm: both_strands=True at l=16 is served by gkm_cross only (the "
@@ -203,8 +205,34 @@ class GramEngine:
                                      "its diagonal would be 0 under normalize=True")
         return self._run(p, seqs, out_dtype)
 
+    @staticmethod
+    def _gkm_weights(side, weights, seqs, l, normalize):
+        """uint8 [n, ldw] of one side's position weights (None stays None); ValueError for a
+        row with too few entries, a value outside 0..255 and, under normalize, a row whose valid
+        words all have weight 0."""
+        if weights is None:
+            return None
+        rows = list(weights)
+        if len(rows) != len(seqs):
+            raise ValueError(f"gkm: weights_{side} has {len(rows)} rows for {len(seqs)} sequences")
+        words = [max(0, len(s) - l + 1) for s in seqs]
+        out = np.zeros((len(seqs), max(words + [1])), dtype=np.uint8)
+        for i, (w, nw, s) in enumerate(zip(rows, words, seqs)):
+            w = np.asarray(w)
+            if w.ndim != 1 or w.shape[0] < nw:
+                raise ValueError(f"gkm: weights_{side}[{i}] needs {nw} entries (one a word)")
+            w = w[:nw]
+            if w.dtype.kind not in "iu" or (nw and (w.min() < 0 or w.max() > 255)):
+                raise ValueError(f"gkm: weights_{side}[{i}] must be integers in 0..255")
+            out[i, :nw] = w
+            if normalize and not any(out[i, a] and set(s[a:a + l]) <= set("ACGT")
+                                     for a in range(nw)):
+                raise ValueError(f"gkm: every valid word of sequence {i} of side {side} has "
+                                 "weight 0; its diagonal would be 0 under normalize=True")
+        return out
+
     def gkm_cross(self, seqs_a, seqs_b, l, k, d=None, normalize=True, out_dtype=L.KMG_F64, *,
-                  both_strands=False):
+                  both_strands=False, weights_a=None, weights_b=None):
         """Rectangular gapped k-mer block [len(seqs_a), len(seqs_b)]:
         K_ij = sum_{a,b} h[ham(A_i[a:a+l], B_j[b:b+l])] with ``gkm``'s h and word rules, rows
         of any length, T^16 counted (kmg_gkm_cross: int8 MFMA).  This is K(queries, support
@@ -212,9 +240,19 @@ class GramEngine:
         longer than ``gkm`` takes.  normalize=True divides by sqrt(K(A_i, A_i) K(B_j, B_j)),
         and a row without a valid word on either side raises ValueError.  both_strands=True:
         K(A_i, B_j) + K(A_i, rc(B_j)) in one pass over the same staged words (l = 16 included),
-        normalised by the both-strands diagonals."""
+        normalised by the both-strands diagonals.
+        weights_a / weights_b (the position-weighted kernel, LS-GKM's wgkm; kmg_gkm_cross_w): a
+        sequence of per-row integer arrays, or one 2-D array, row i with at least
+        len(seq_i) - l + 1 entries in 0..255 (``params.gkm_center_weights``); the word starting at
+        letter a of row i counts with weight [i][a], a pair with the product of its two
+        weights, a reverse-complement word with the weight of the window it was made from, and
+        the normalising diagonals with their own side's weights.  None is all ones.  Bad shapes
+        or values and, under normalize=True, a row whose valid words all weigh 0 raise
+        ValueError before any device work."""
         p = P.gkm(l, k, d, normalize, both_strands)
         seqs_a, seqs_b = list(seqs_a), list(seqs_b)
+        wa = self._gkm_weights("a", weights_a, seqs_a, int(l), normalize)
+        wb = self._gkm_weights("b", weights_b, seqs_b, int(l), normalize)
         if normalize:
             if out_dtype == L.KMG_I32:
                 raise ValueError("gkm: normalised output needs a floating dtype")
@@ -229,7 +267,7 @@ class GramEngine:
             return np.zeros((len(seqs_a), len(seqs_b)), dtype=L.DTYPES[out_dtype])
         codes_a, lens_a = E.encode(seqs_a)
         codes_b, lens_b = E.encode(seqs_b)
-        return self.ctx.gkm_cross(p, codes_a, lens_a, codes_b, lens_b, out_dtype)
+        return self.ctx.gkm_cross(p, codes_a, lens_a, codes_b, lens_b, out_dtype, wa, wb)
 
     # ------------------------------------------------------------------ scoring
     def scorer(self, method, seqs, coef):

@@ -60,6 +60,21 @@ def gkm(l, k, d=None, normalize=True, both_strands=False):
                 strands=2 if both_strands else 0)
 
 
+def gkm_center_weights(length, l, M=50, H=50):
+    """uint8 position weights of the words a = 0 .. length - l of a row of ``length`` letters,
+    for the weighted gkm kernel (``GramEngine.gkm_cross(weights_a=, weights_b=)``):
+    min(255, floor(M * 2 ** (-D_a / H)) + 1), D_a = |2a + l - length| / 2 the distance from the
+    word's centre to the row's centre, so the weight is M + 1 at the centre and halves every H
+    letters.  Modelled on the -M / -H options of LS-GKM's centre-weighted kernel (wgkm); LS-GKM
+    was not at hand when this was written, so parity with its weights is unpinned."""
+    import numpy as np
+    length, l, M, H = int(length), int(l), int(M), int(H)
+    if M < 0 or H < 1:
+        raise ValueError(f"gkm_center_weights: M={M} must be >= 0 and H={H} >= 1")
+    return np.array([min(255, int(M * 2.0 ** (-abs(2 * a + l - length) / 2 / H)) + 1)
+                     for a in range(max(0, length - l + 1))], dtype=np.uint8)
+
+
 def make(kind, **kw):
     """Fill a KmgParams struct."""
     p = L.KmgParams()

@@ -17,6 +17,12 @@ profiles/gkm_strands_timing.json: at the same sizes, one both-strands call (stra
 reverse-complemented on the host), "gkmx" stages, alternated in one process; and at the first
 size one both-strands square call (kmg_gram_device, all rows, SYM) against twice the
 single-strand "gkm" stage.  A both-strands call counts two evaluations a word pair.
+
+--weighted times the position-weighted kernel of DESIGN.md §6g instead and writes
+profiles/gkm_weighted_timing.json: at the same sizes and at the long-row point, the weighted
+call (kmg_gkm_cross_w_device, seeded uniform 0..255 weights on both sides) against the
+unweighted one (kmg_gkm_cross_device) on the same rows, raw float64 (int32 is refused at these
+weights), "gkmx" stages, alternated in one process; once with one strand, once with both.
 """
 import argparse
 import ctypes
@@ -154,6 +160,55 @@ def run_strands(ctx, n, reps, rng):
             "sampled_entries_wrong": bad, "sampled_entries": len(pairs)}
 
 
+def run_weighted(ctx, codes, lens, h, reps, rng, both):
+    """rows [0, h) x rows [h, n): the weighted gkmx stage against the unweighted one."""
+    n, ldc = codes.shape[0], codes.shape[1]
+    length = int(lens.max())
+    pw = length - LW + 1
+    wts = np.random.default_rng(13).integers(0, 256, (n, pw)).astype(np.uint8)
+    bufs = [ctx.dmalloc(a.nbytes) for a in (codes, lens, wts)] + [ctx.dmalloc(8 * h * (n - h))]
+    d_codes, d_lens, d_wts, d_K = bufs
+    for d, a in zip(bufs, (codes, lens, wts)):
+        ctx.h2d(d, a)
+    p = P.gkm(LW, KI, D, normalize=False, both_strands=both)
+    ctx.set_timing(True)
+    d_b, d_lb = at(d_codes, h * ldc), at(d_lens, 4 * h)
+    dev = {"plain": [], "weighted": []}
+    for rep in range(reps + 1):  # one warm-up round of both routes; "weighted" last: it is checked
+        ctx.gkm_cross_device(p, d_codes, d_lens, h, ldc, d_b, d_lb, n - h, ldc, L.KMG_F64, d_K, n - h)
+        ctx.synchronize()
+        if rep >= 1:
+            dev["plain"].append(ctx.stage_ms("gkmx"))
+        ctx.gkm_cross_w_device(p, d_codes, d_lens, h, ldc, d_wts, pw, d_b, d_lb, n - h, ldc,
+                               at(d_wts, h * pw), pw, L.KMG_F64, d_K, n - h)
+        ctx.synchronize()
+        if rep >= 1:
+            dev["weighted"].append(ctx.stage_ms("gkmx"))
+    K = ctx.d2h(np.empty((h, n - h), dtype=np.float64), d_K)
+    hh = np.array(P.gkm_weights(LW, KI, D), dtype=np.int64)
+    win = np.lib.stride_tricks.sliding_window_view
+
+    def formula_w(i, j):
+        x, y = win(codes[i, :length], LW), win(codes[h + j, :length], LW)
+        H = hh[(x[:, None, :] != y[None, :, :]).sum(-1)]
+        if both:
+            H = H + hh[(x[:, None, :] != (y[:, ::-1] ^ 3)[None, :, :]).sum(-1)]
+        return int(wts[i].astype(np.int64) @ H @ wts[h + j].astype(np.int64))
+    pairs = [(0, 0), (h - 1, n - h - 1)] + [(int(rng.integers(0, h)), int(rng.integers(0, n - h)))
+                                            for _ in range(14)]
+    bad = sum(int(K[i, j]) != formula_w(i, j) for i, j in pairs)
+    for d in bufs:
+        ctx.dfree(d)
+    med = {r: float(np.median(v)) for r, v in dev.items()}
+    evals = (2 if both else 1) * h * (n - h) * pw * pw
+    return {"n": n, "rows_a": h, "rows_b": n - h, "length": length, "words_a_row": pw, "reps": reps,
+            "strands": 2 if both else 1, "stage_ms_median": med, "stage_ms_all": dev,
+            "plain_spread": (max(dev["plain"]) - min(dev["plain"])) / med["plain"],
+            "ratio_weighted_over_plain": med["weighted"] / med["plain"], "evaluations": evals,
+            "evaluations_per_s": {r: evals / (med[r] * 1e-3) for r in med},
+            "sampled_entries_wrong": bad, "sampled_entries": len(pairs)}
+
+
 def run_strands_square(ctx, n, reps, rng):
     """square: one both-strands kmg_gram_device call (SYM) vs twice the single-strand stage."""
     codes, lens = E.synthetic(n, 101, seed=5)
@@ -192,9 +247,25 @@ def main():
     ap.add_argument("--long", default="256x1000")
     ap.add_argument("--strands", action="store_true",
                     help="the both-strands comparison (DESIGN.md §6f) instead of the routes above")
+    ap.add_argument("--weighted", action="store_true",
+                    help="the position-weighted kernel against the unweighted one (DESIGN.md §6g)")
     a = ap.parse_args()
     ctx = L.Context(0)
     rng = np.random.default_rng(12)
+    if a.weighted:
+        ln, ll = (int(v) for v in a.long.split("x"))
+        sets = [E.synthetic(int(n), 101, seed=5) + (int(n) // 2,) for n in a.sizes.split(",")]
+        cl, ll_ = E.synthetic(ln, ll, seed=6)
+        sets.append((np.concatenate([cl, cl]), np.concatenate([ll_, ll_]), ln))  # the rows x themselves
+        res = {"l": LW, "k": KI, "d": D}
+        for name, both in (("one_strand", False), ("both_strands", True)):
+            res[name] = [run_weighted(ctx, c, n_, h, a.reps, rng, both) for c, n_, h in sets]
+        ctx.close()
+        with open(a.out.replace("gkm_cross_timing.json", "gkm_weighted_timing.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps([{k: v for k, v in r.items() if k != "stage_ms_all"}
+                          for r in res["one_strand"] + res["both_strands"]]))
+        return
     if a.strands:
         sizes = [int(n) for n in a.sizes.split(",")]
         res = {"l": LW, "k": KI, "d": D, "cross": [run_strands(ctx, n, a.reps, rng) for n in sizes],
