@@ -221,6 +221,70 @@ int kmg_gkm_cross_w_device(kmg_ctx *ctx, const kmg_params *p, const uint8_t *d_c
                            int64_t ld_out);
 
 /*
+ * Mismatch profile of the gapped k-mer kernels, the quantity gkm-SVM and LS-GKM compute
+ * underneath every variant of the kernel:
+ *   out[i][j][m] = N_m(A_i, B_j) = #{(a, b) : ham(A_i[a:a+l], B_j[b:b+l]) = m},  m = 0 .. d
+ * int64, laid out [na][ld_out][d + 1] (ld_out >= nb pairs a row).  Sequences, word rules and row
+ * lengths as in kmg_gkm_cross; l = p->k, d = p->m with 0 <= d <= l - 1, and p->g is only checked
+ * to be >= d (KMG_GKM's parameter rule): no weight h enters.  p->strands = 2 adds the counts
+ * against the reverse complement, #{(a, b) : ham(A_i word a, rc(B_j word b)) = m}, into the same
+ * bins.  p->normalize is ignored.  The bin m = l is not produced (d <= l - 1): a word pair
+ * without a single match looks the same to the kernel as an absent or invalid word.  It is
+ * strands * valid_a(i) * valid_b(j) - sum of the bins 0 .. l - 1, valid_x the count of all-ACGT
+ * words of a row, which the caller can form.
+ * The counts come from the int8 MFMA products of kmg_gkm_cross with a packed counter in place
+ * of the weight in the lookup table, four bins a pass, ceil((d + 1) / 4) passes
+ * (gram_gkmx_kernel<.., PF>, kmg_gkmx.hip), and are exact.  A kind other than KMG_GKM is
+ * KMG_EUNSUPPORTED; na = 0 or nb = 0 returns KMG_OK and writes nothing; all checks come before
+ * any allocation or launch.  The kernel time counts under stage "gkmx".  Host buffers in and
+ * out, synchronous.
+ */
+int kmg_gkm_profile(kmg_ctx *ctx, const kmg_params *p, const uint8_t *codes_a,
+                    const int32_t *lens_a, int64_t na, int64_t ldc_a, const uint8_t *codes_b,
+                    const int32_t *lens_b, int64_t nb, int64_t ldc_b, int64_t *out,
+                    int64_t ld_out);
+/* The same on device pointers (rows up to ldc_a / ldc_b symbols bound the checks), on the
+ * context stream, without synchronising. */
+int kmg_gkm_profile_device(kmg_ctx *ctx, const kmg_params *p, const uint8_t *d_codes_a,
+                           const int32_t *d_lens_a, int64_t na, int64_t ldc_a,
+                           const uint8_t *d_codes_b, const int32_t *d_lens_b, int64_t nb,
+                           int64_t ldc_b, int64_t *d_out, int64_t ld_out);
+
+/*
+ * Gapped k-mer block under a caller's filter: real coefficients c[m] = filter[m] in place of
+ * the integers C(l - m, k),
+ *   out[i][j] = sum_{m = 0 .. d} filter[m] N_m(A_i, B_j)          (N_m: kmg_gkm_profile)
+ * the form of the estimated l-mer kernels of gkm-SVM 2.0 / LS-GKM (truncated or full filter;
+ * the coefficients are the caller's).  d = p->m, nfilter must be d + 1 (else KMG_EINVAL);
+ * filter is a host pointer in both forms and is passed to the kernels by value.  With
+ * filter[m] = C(l - m, k) the result is bit for bit that of kmg_gkm_cross.
+ * The profile is exact; the sum is float64 in ascending m with every product and sum rounded
+ * on its own,  x = ((c[0] N_0 + c[1] N_1) + c[2] N_2) + ...,  so a host restatement gives the
+ * same bits, and it does not depend on the route: d <= 3 is one pass with the filter in the
+ * kernel's epilogue, a longer filter stores the profile of a row slab in a context workspace
+ * (256 MB at most, or one 16-row tile) and a small kernel applies the same expression (stage
+ * "combine").  p->normalize = 1: x / (sqrt(x(A_i, A_i)) * sqrt(x(B_j, B_j))), one division,
+ * the diagonals from the same expression and IEEE sqrt; a filter that makes a diagonal zero
+ * or negative gives what IEEE gives there (inf / NaN), as a row without a word does.
+ * out_dtype KMG_F64, or KMG_F32 (the float64 value rounded once); KMG_I32 is KMG_EINVAL.
+ * strands * P_a * P_b >= 2^53 (under normalize = 1 also a diagonal's strands * P_x^2) is
+ * KMG_EUNSUPPORTED, so every bin converts exactly.  Kinds, empty sides and the order of the
+ * checks as in kmg_gkm_cross.  Position weights are not served together with a filter.
+ * Host buffers in and out, synchronous.
+ */
+int kmg_gkm_cross_f(kmg_ctx *ctx, const kmg_params *p, const uint8_t *codes_a,
+                    const int32_t *lens_a, int64_t na, int64_t ldc_a, const uint8_t *codes_b,
+                    const int32_t *lens_b, int64_t nb, int64_t ldc_b, const double *filter,
+                    int32_t nfilter, int32_t out_dtype, void *out, int64_t ld_out);
+/* The same on device pointers (filter stays a host pointer: no upload, no synchronisation), on
+ * the context stream. */
+int kmg_gkm_cross_f_device(kmg_ctx *ctx, const kmg_params *p, const uint8_t *d_codes_a,
+                           const int32_t *d_lens_a, int64_t na, int64_t ldc_a,
+                           const uint8_t *d_codes_b, const int32_t *d_lens_b, int64_t nb,
+                           int64_t ldc_b, const double *filter, int32_t nfilter,
+                           int32_t out_dtype, void *d_out, int64_t ld_out);
+
+/*
  * Device-resident column block: K[i][col0 + j] for every row i in [0, n) and j in
  * [0, col1 - col0), at d_out[i * ld_out + j].  K is symmetric, so this is the row slab
  * [col0, col1) x all n transposed: one GPU's 1/G share of a sharded build (the pair loops
@@ -442,7 +506,8 @@ int kmg_stream(kmg_ctx *ctx, void **hip_stream);
  * lists), "lists" (neighbourhood-list sizes and starts), "combine",
  * "vtab" / "butterfly" / "score" (kmg_scorer_*: weight table, Hamming DP, query scoring),
  * "gkm" (the tiled gapped k-mer Gram kernel, inside the call's "gram" stage),
- * "gkmx" (the rectangular gkm kernel of kmg_gkm_cross*; its diagonals count under "diag"),
+ * "gkmx" (the rectangular gkm kernel of kmg_gkm_cross* and kmg_gkm_profile*; its diagonals
+ * count under "diag", the filter kernel of kmg_gkm_cross_f* past four bins under "combine"),
  * "solve", "memset", "gather" (the RCCL all-gathers of kmg_gram_blocks, timed on their own
  * stream), "unpack" (round-slab assembly), "mirror" (lower block triangle of a full square
  * mismatch K built by its upper block triangle).

@@ -166,6 +166,9 @@ struct Tuning {
   int dense_half = -1;      // KMG_DENSE_HALF: dense Gram tiles over two 4-wave workgroups (BK
                             // 64), -1: when dp <= 1024 (SP k=5 N=20000 0.41 -> 0.39 ms; at
                             // dp >= 4096 BK 128 wins; profiles/r02bj_dense_epilogue_ab.jsonl)
+  int gkm_prof_ws = 256;    // KMG_GKM_PROF_WS: MB of profile workspace a row slab of kmg_gkm_cross_f
+                            // may take where the filter has more than four bins (a slab is one
+                            // 16-row tile at the least: 0 gives 16-row slabs)
   int check = 0;            // KMG_CHECK: 1 validate the neighbourhood lists' metadata after
                             // every fill (nb_check_kernel; one host sync a build) and fail with
                             // KMG_EINTERNAL before any Gram launch reads past a list; 2 the
@@ -212,6 +215,7 @@ void read_tuning(Tuning &t) {
   t.dense_sb = env_or("KMG_DENSE_SB", d.dense_sb);
   t.dense_bk = env_or("KMG_DENSE_BK", d.dense_bk);
   t.dense_half = env_or("KMG_DENSE_HALF", d.dense_half);
+  t.gkm_prof_ws = std::max(0, std::min(65536, env_or("KMG_GKM_PROF_WS", d.gkm_prof_ws)));
   t.check = env_or("KMG_CHECK", d.check);
   if (getenv("KMG_MM_CHUNK") == nullptr) t.mm_chunk = 0;  // 0: per-formulation default
 }
@@ -247,6 +251,7 @@ struct kmg_ctx {
                                     // the validity bits of A, then B
   DevBuf gx_wts, gx_wts_in;         // kmg_gkm_cross_w: the laid-out weights of A, then B; the
                                     // host path's copies of the caller's arrays
+  DevBuf gx_prof;                   // kmg_gkm_cross_f, filters past four bins: a row slab's profile
   Tuning tune;
   DevBuf cmb_k, cmb_ptrs, cmb_vec, cmb_out, cmb_tmp;  // combination consumers (host path)
   DevBuf sv_mat, sv_vec, sv_info;  // dense learners: factorised system, vectors, info/ipiv
@@ -1662,7 +1667,7 @@ int kmg_destroy(kmg_ctx *c) {
                     &c->tri_stage, &c->tri_scratch, &c->dense_tiles, &c->ovf, &c->slabs,
                     &c->gcoef, &c->feat32, &c->k32, &c->ft_cols,
                     &c->nb_seg, &c->nb_use, &c->nb_lines, &c->chk, &c->cb_scratch,
-                    &c->sc_fix, &c->sc_tab, &c->gx_words_b, &c->gx_bits};
+                    &c->sc_fix, &c->sc_tab, &c->gx_words_b, &c->gx_bits, &c->gx_prof};
   for (DevBuf *b : bufs) b->release();
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
   if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
@@ -1840,13 +1845,22 @@ static int gkm_cross_check(const kmg_params *p, int64_t na, int64_t ldc_a, int64
   return gkm_check(p, dt, wt);
 }
 
+// kmg_gkm_profile* and kmg_gkm_cross_f*: the call wants the mismatch profile itself
+// (f = nullptr) or sum_m f->c[m] N_m
+struct GkmPfCall {
+  const GkmFilter *f;
+};
+
 // ... and the bounds of a call whose rows are at most maxlen_a / maxlen_b symbols long
-// (kmg_gkm_cross_w*: a weighted side counts every word up to 255 times, wa / wb = 255, else 1)
+// (kmg_gkm_cross_w*: a weighted side counts every word up to 255 times, wa / wb = 255, else 1;
+// pf: the bins are bounded instead of the weighted sum, and int64 bins by the row limits alone)
 static int gkm_cross_bounds(const kmg_params *p, const GkmWeights &wt, int maxlen_a, int64_t na,
-                            int maxlen_b, int64_t nb, int32_t dt, int wa = 1, int wb = 1) {
+                            int maxlen_b, int64_t nb, int32_t dt, int wa = 1, int wb = 1,
+                            const GkmPfCall *pf = nullptr) {
   const int l = p->k;
   const int pa = std::max(1, maxlen_a - l + 1), pb = std::max(1, maxlen_b - l + 1);
-  const double two53 = 9007199254740992.0, h0 = (double)wt.h[0];
+  const double two53 = pf && !pf->f ? INFINITY : 9007199254740992.0;
+  const double h0 = pf ? 1.0 : (double)wt.h[0];
   // every raw value is an exact integer in float64 (and in int32 where that is the output);
   // both strands count twice the pairs, in the block and in the diagonals
   const double ns = p->strands == 2 ? 2.0 : 1.0;
@@ -1869,15 +1883,79 @@ static int gkm_cross_bounds(const kmg_params *p, const GkmWeights &wt, int maxle
   return KMG_OK;
 }
 
+// the profile kernels over the extracted sides: the bins themselves at d_out [na][ld][d + 1], or
+// the filtered values.  d <= 3 is one pass with the filter in its epilogue; a longer filter goes
+// through the profile of a row slab in the workspace (Tuning::gkm_prof_ws MB at most, unless one
+// tile row of 16 is more) and gkm_filter_kernel, with the same expression.  The diagonals of
+// the normalisation go the same two ways.
+static int gkm_pf_launch(kmg_ctx *c, const kmg_params *p, const GkmPfCall &pf, const GkmxSide &A,
+                         const GkmxSide &B, int32_t dt, void *d_out, int64_t ld) {
+  const int l = p->k, d = p->m;
+  const bool rc = p->strands == 2;
+  if (!pf.f) {
+    StageTimer t(c, ST_GKMX);
+    KMG_HIP(launch_gkmx_profile(A, B, l, d, rc, 0, A.n, (int64_t *)d_out, ld, c->stream));
+    return KMG_OK;
+  }
+  const bool fused = d <= 3;
+  const size_t per_row = sizeof(int64_t) * (size_t)B.n * (d + 1);
+  const int64_t ws_rows = (int64_t)(((size_t)c->tune.gkm_prof_ws << 20) / per_row);
+  const int64_t slab = std::min<int64_t>(A.n, std::max<int64_t>(16, ws_rows / 16 * 16));
+  if (!fused) {
+    const size_t diag = p->normalize ? sizeof(int64_t) * (size_t)std::max(A.n, B.n) * (d + 1) : 0;
+    KMG_TRY(c->gx_prof.ensure(std::max((size_t)slab * per_row, diag)));
+  }
+  int64_t *prof = c->gx_prof.as<int64_t>();
+  OutSpec o{d_out, ld, dt, 0, nullptr, nullptr};
+  const double *sa = nullptr, *sb = nullptr;
+  if (p->normalize) {  // sa in diagv, sb in dsq
+    KMG_TRY(c->diagv.ensure(sizeof(double) * (size_t)A.n));
+    KMG_TRY(c->dsq.ensure(sizeof(double) * (size_t)B.n));
+    StageTimer t(c, ST_DIAG);
+    for (int side = 0; side < 2; ++side) {
+      const GkmxSide &S = side ? B : A;
+      double *dq = side ? c->dsq.as<double>() : c->diagv.as<double>();
+      if (fused) {
+        KMG_HIP(launch_gkmx_filtered_diag(S, l, d, rc, *pf.f, dq, c->stream));
+      } else {
+        KMG_HIP(launch_gkmx_profile_diag(S, l, d, rc, prof, c->stream));
+        KMG_HIP(launch_gkm_filter(prof, S.n, 1, 1, d, *pf.f, OutSpec{}, nullptr, nullptr, dq, c->stream));
+      }
+    }
+    o.normalize = 1;
+    sa = c->diagv.as<double>();
+    sb = c->dsq.as<double>();
+  }
+  if (fused) {
+    StageTimer t(c, ST_GKMX);
+    KMG_HIP(launch_gkmx_filtered(A, B, l, d, rc, *pf.f, o, sa, sb, c->stream));
+    return KMG_OK;
+  }
+  for (int64_t r0 = 0; r0 < A.n; r0 += slab) {
+    const int64_t rows = std::min(slab, A.n - r0);
+    {
+      StageTimer t(c, ST_GKMX);
+      KMG_HIP(launch_gkmx_profile(A, B, l, d, rc, r0, rows, prof, B.n, c->stream));
+    }
+    StageTimer t(c, ST_COMBINE);
+    OutSpec os = o;
+    os.out = (char *)d_out + (size_t)r0 * ld * dtype_size(dt);
+    KMG_HIP(launch_gkm_filter(prof, rows, B.n, B.n, d, *pf.f, os, sa ? sa + r0 : nullptr, sb, nullptr,
+                              c->stream));
+  }
+  return KMG_OK;
+}
+
 // device rows of both sides -> words + validity bits, sqrt(K_ii) of both sides under
 // normalisation (the same kernel over the pairs (i, i)), then the rectangular kernel
-// (kmg_gkmx.hip); na, nb > 0 and gkm_cross_bounds has passed
+// (kmg_gkmx.hip); na, nb > 0 and gkm_cross_bounds has passed.  pf: the profile kernels instead
 static int gkm_cross_device(kmg_ctx *c, const kmg_params *p, const GkmWeights &wt,
                             const uint8_t *d_ca, const int32_t *d_la, int maxlen_a, int64_t na,
                             int64_t ldc_a, const uint8_t *d_cb, const int32_t *d_lb, int maxlen_b,
                             int64_t nb, int64_t ldc_b, int32_t dt, void *d_out, int64_t ld,
                             const uint8_t *d_wa = nullptr, int64_t ldw_a = 0,
-                            const uint8_t *d_wb = nullptr, int64_t ldw_b = 0) {
+                            const uint8_t *d_wb = nullptr, int64_t ldw_b = 0,
+                            const GkmPfCall *pf = nullptr) {
   c->last_call_first = (int)c->ev_log.size();
   const int l = p->k;
   const bool rc = p->strands == 2;
@@ -1916,6 +1994,7 @@ static int gkm_cross_device(kmg_ctx *c, const kmg_params *p, const GkmWeights &w
     if (q.w)
       KMG_HIP(launch_gkmx_weights(q.w, q.ldw, q.lens, q.n, l, q.pmax, (uint8_t *)q.wts, c->stream));
   }
+  if (pf) return gkm_pf_launch(c, p, *pf, A, B, dt, d_out, ld);
   OutSpec o{d_out, ld, dt, 0, nullptr, nullptr};
   const double *sa = nullptr, *sb = nullptr;
   if (p->normalize) {  // sa in diagv, sb in dsq
@@ -1948,14 +2027,14 @@ static int gkm_cross_device_entry(kmg_ctx *c, const kmg_params *p, const uint8_t
                                   const uint8_t *d_wa, int64_t ldw_a, const uint8_t *d_codes_b,
                                   const int32_t *d_lens_b, int64_t nb, int64_t ldc_b,
                                   const uint8_t *d_wb, int64_t ldw_b, int32_t out_dtype,
-                                  void *d_out, int64_t ld_out) {
+                                  void *d_out, int64_t ld_out, const GkmPfCall *pf = nullptr) {
   if (!c) return fail(KMG_EINVAL, "ctx is NULL");
   std::lock_guard<std::mutex> lk(c->mu);
   GkmWeights wt{};
   KMG_TRY(gkm_cross_check(p, na, ldc_a, nb, ldc_b, out_dtype, wt));
   // (device rows: the lengths are device data, so ldc bounds them, as in kmg_gram_device)
   KMG_TRY(gkm_cross_bounds(p, wt, (int)ldc_a, na, (int)ldc_b, nb, out_dtype, d_wa ? 255 : 1,
-                           d_wb ? 255 : 1));
+                           d_wb ? 255 : 1, pf));
   KMG_TRY(gkm_cross_ldw(p, d_wa, ldw_a, (int)ldc_a, 'a'));
   KMG_TRY(gkm_cross_ldw(p, d_wb, ldw_b, (int)ldc_b, 'b'));
   if (na == 0 || nb == 0) return KMG_OK;
@@ -1964,7 +2043,8 @@ static int gkm_cross_device_entry(kmg_ctx *c, const kmg_params *p, const uint8_t
   if (ld_out < nb) return fail(KMG_EINVAL, "ld_out < nb");
   KMG_HIP(hipSetDevice(c->device));
   return gkm_cross_device(c, p, wt, d_codes_a, d_lens_a, (int)ldc_a, na, ldc_a, d_codes_b, d_lens_b,
-                          (int)ldc_b, nb, ldc_b, out_dtype, d_out, ld_out, d_wa, ldw_a, d_wb, ldw_b);
+                          (int)ldc_b, nb, ldc_b, out_dtype, d_out, ld_out, d_wa, ldw_a, d_wb, ldw_b,
+                          pf);
 }
 
 int kmg_gkm_cross_device(kmg_ctx *c, const kmg_params *p, const uint8_t *d_codes_a,
@@ -1990,7 +2070,7 @@ static int gkm_cross_host_entry(kmg_ctx *c, const kmg_params *p, const uint8_t *
                                 const uint8_t *wts_a, int64_t ldw_a, const uint8_t *codes_b,
                                 const int32_t *lens_b, int64_t nb, int64_t ldc_b,
                                 const uint8_t *wts_b, int64_t ldw_b, int32_t out_dtype, void *out,
-                                int64_t ld_out) {
+                                int64_t ld_out, const GkmPfCall *pf = nullptr) {
   if (!c) return fail(KMG_EINVAL, "ctx is NULL");
   std::lock_guard<std::mutex> lk(c->mu);
   GkmWeights wt{};
@@ -2010,14 +2090,15 @@ static int gkm_cross_host_entry(kmg_ctx *c, const kmg_params *p, const uint8_t *
     }
   }
   KMG_TRY(gkm_cross_bounds(p, wt, maxlen[0], na, maxlen[1], nb, out_dtype, wts_a ? 255 : 1,
-                           wts_b ? 255 : 1));
+                           wts_b ? 255 : 1, pf));
   if (!empty) {
     KMG_TRY(gkm_cross_ldw(p, wts_a, ldw_a, maxlen[0], 'a'));
     KMG_TRY(gkm_cross_ldw(p, wts_b, ldw_b, maxlen[1], 'b'));
   }
   if (empty) return KMG_OK;
   KMG_HIP(hipSetDevice(c->device));
-  const size_t esz = dtype_size(out_dtype);
+  // (a profile call's element is the d + 1 int64 bins of a pair)
+  const size_t esz = pf && !pf->f ? sizeof(int64_t) * (size_t)(p->m + 1) : dtype_size(out_dtype);
   const int64_t ldd = (nb + 3) & ~3LL;
   const size_t bytes_a = ((size_t)na * ldc_a + 15) & ~(size_t)15;
   KMG_TRY(c->h_codes.ensure(bytes_a + (size_t)nb * ldc_b));
@@ -2046,7 +2127,7 @@ static int gkm_cross_host_entry(kmg_ctx *c, const kmg_params *p, const uint8_t *
     if (wts_b) d_wb = d_w + sz_a;
   }
   KMG_TRY(gkm_cross_device(c, p, wt, d_ca, d_la, maxlen[0], na, ldc_a, d_cb, d_lb, maxlen[1], nb,
-                           ldc_b, out_dtype, c->h_out.p, ldd, d_wa, ldw_a, d_wb, ldw_b));
+                           ldc_b, out_dtype, c->h_out.p, ldd, d_wa, ldw_a, d_wb, ldw_b, pf));
   KMG_HIP(hipMemcpy2DAsync(out, (size_t)ld_out * esz, c->h_out.p, (size_t)ldd * esz,
                            (size_t)nb * esz, (size_t)na, hipMemcpyDeviceToHost, c->stream));
   KMG_HIP(hipStreamSynchronize(c->stream));
@@ -2067,6 +2148,61 @@ int kmg_gkm_cross_w(kmg_ctx *c, const kmg_params *p, const uint8_t *codes_a, con
                     int64_t ld_out) {
   return gkm_cross_host_entry(c, p, codes_a, lens_a, na, ldc_a, wts_a, ldw_a, codes_b, lens_b, nb,
                               ldc_b, wts_b, ldw_b, out_dtype, out, ld_out);
+}
+
+int kmg_gkm_profile(kmg_ctx *c, const kmg_params *p, const uint8_t *codes_a, const int32_t *lens_a,
+                    int64_t na, int64_t ldc_a, const uint8_t *codes_b, const int32_t *lens_b,
+                    int64_t nb, int64_t ldc_b, int64_t *out, int64_t ld_out) {
+  const GkmPfCall pf{nullptr};
+  return gkm_cross_host_entry(c, p, codes_a, lens_a, na, ldc_a, nullptr, 0, codes_b, lens_b, nb,
+                              ldc_b, nullptr, 0, KMG_F64, out, ld_out, &pf);
+}
+
+int kmg_gkm_profile_device(kmg_ctx *c, const kmg_params *p, const uint8_t *d_codes_a,
+                           const int32_t *d_lens_a, int64_t na, int64_t ldc_a,
+                           const uint8_t *d_codes_b, const int32_t *d_lens_b, int64_t nb,
+                           int64_t ldc_b, int64_t *d_out, int64_t ld_out) {
+  const GkmPfCall pf{nullptr};
+  return gkm_cross_device_entry(c, p, d_codes_a, d_lens_a, na, ldc_a, nullptr, 0, d_codes_b,
+                                d_lens_b, nb, ldc_b, nullptr, 0, KMG_F64, d_out, ld_out, &pf);
+}
+
+// kmg_gkm_cross_f*: the filter's own rules, ahead of everything else
+static int gkm_filter_check(const kmg_params *p, const double *filter, int32_t nfilter, int32_t dt,
+                            GkmFilter &f) {
+  if (!p) return fail(KMG_EINVAL, "params is NULL");
+  if (p->kind != KMG_GKM)
+    return fail(KMG_EUNSUPPORTED, "gkm cross: kernel kind %d is not KMG_GKM", p->kind);
+  if (!filter) return fail(KMG_EINVAL, "gkm cross: filter is NULL");
+  if (nfilter != p->m + 1 || nfilter < 1 || nfilter > 16)
+    return fail(KMG_EINVAL, "gkm cross: a filter of %d coefficients for m = 0..%d", nfilter, p->m);
+  if (dt == KMG_I32) return fail(KMG_EINVAL, "gkm cross: a filtered block needs a floating dtype");
+  f = GkmFilter{};
+  for (int m = 0; m < nfilter; ++m) f.c[m] = filter[m];
+  return KMG_OK;
+}
+
+int kmg_gkm_cross_f(kmg_ctx *c, const kmg_params *p, const uint8_t *codes_a, const int32_t *lens_a,
+                    int64_t na, int64_t ldc_a, const uint8_t *codes_b, const int32_t *lens_b,
+                    int64_t nb, int64_t ldc_b, const double *filter, int32_t nfilter,
+                    int32_t out_dtype, void *out, int64_t ld_out) {
+  GkmFilter f;
+  KMG_TRY(gkm_filter_check(p, filter, nfilter, out_dtype, f));
+  const GkmPfCall pf{&f};
+  return gkm_cross_host_entry(c, p, codes_a, lens_a, na, ldc_a, nullptr, 0, codes_b, lens_b, nb,
+                              ldc_b, nullptr, 0, out_dtype, out, ld_out, &pf);
+}
+
+int kmg_gkm_cross_f_device(kmg_ctx *c, const kmg_params *p, const uint8_t *d_codes_a,
+                           const int32_t *d_lens_a, int64_t na, int64_t ldc_a,
+                           const uint8_t *d_codes_b, const int32_t *d_lens_b, int64_t nb,
+                           int64_t ldc_b, const double *filter, int32_t nfilter, int32_t out_dtype,
+                           void *d_out, int64_t ld_out) {
+  GkmFilter f;
+  KMG_TRY(gkm_filter_check(p, filter, nfilter, out_dtype, f));
+  const GkmPfCall pf{&f};
+  return gkm_cross_device_entry(c, p, d_codes_a, d_lens_a, na, ldc_a, nullptr, 0, d_codes_b,
+                                d_lens_b, nb, ldc_b, nullptr, 0, out_dtype, d_out, ld_out, &pf);
 }
 
 int kmg_gram_device_cols(kmg_ctx *c, const kmg_params *p, const uint8_t *d_codes,

@@ -19,7 +19,7 @@
 //
 // gkmx_extract_kernel   packed records -> words [n][32 nblk] (0 where invalid) and validity
 //                       bits [n][nblk], nblk = ceil(pmax / 32) blocks of 32 words a row.
-// gram_gkmx_kernel<DIAG, TWO, RC, WT>   one 256-thread workgroup a tile of 16 rows x 8 columns.
+// gram_gkmx_kernel<DIAG, TWO, RC, WT, PF>   one 256-thread workgroup a tile of 16 rows x 8 columns.
 //   LDS     one chunk of 8 blocks (256 words) of every tile row and column, 4 B a word:
 //           16 KB + 8 KB, their validity words (768 B), hm (80 B) and the int64 result tile
 //           (1 KB): 26 KB whatever pmax is.  The chunk loops (A chunks outside, B chunks
@@ -88,7 +88,26 @@
 //           for it in its launch bounds).  LDS: 8 KB + 8 KB of words, 2 KB + 2 KB of weights,
 //           validity, hm, result: 22 KB.  DIAG: sqrt(Kw(x, x)), both sides staged with x's
 //           weights.
+//   PF      the mismatch profile (kmg_gkm_profile*, kmg_gkm_cross_f*): N_m = #{(a, b) : ham = m}
+//           for m = 0 .. d <= l - 1 instead of sum h[ham].  hm holds a packed counter a bin,
+//           hm[mm] = 1 << 8 (m - 4 pass) for the bin m = l - mm of this pass (four bins a pass,
+//           ceil((d + 1) / 4) launches), so the same 16 lookups build a histogram: their sum is
+//           one int32 of four 8-bit fields (each <= 16, RC <= 32), split by two masks into the
+//           pair's two int32 of two 16-bit fields (GxPair; the 64 VGPRs of the int64 sums).  A
+//           16-bit field gains at most 8 x 8 blocks x 16 entries x 2 (RC) = 2048 a chunk pair and
+//           is flushed once a chunk pair: four xor-shuffle steps packed (16 lanes: 32768), then
+//           unpacked to 32 bits for the last two, and lane 0 adds into the pair's int64 bins in
+//           LDS (res[16][8][4], 4 KB; only the owning wave writes a pair: no atomics).  hm[0]
+//           stays 0, so the bin m = l cannot be counted: it is strands * valid_a * valid_b less
+//           the other bins, which the caller can form.  The epilogue stores the pass's bins, or
+//           (one pass, d <= 3) applies the caller's real filter c by value,
+//           x = ((c[0] N_0 + c[1] N_1) + c[2] N_2) + c[3] N_3 with every product and sum rounded
+//           on its own, normalised by one division as above; gkm_filter_kernel applies the same
+//           routine to a stored profile for d > 3.  DIAG: the profiles N_m(x, x), or sqrt(x).
+//           Not with WT: a weighted field needs 12+ bits an add.  LDS 29.5 KB.
 #include "kmg_internal.h"
+
+#include <type_traits>
 
 namespace kmg {
 
@@ -212,13 +231,26 @@ __device__ __forceinline__ int gx_lookup(const int32_t *hm, const v16i &acc) {
   return t;
 }
 
+// what a pair's lane adds a looked-up sum t into: the int64 kernel value, or (PF) the profile's
+// packed counters.  There the table entry of a match count is 1 << 8 (bin & 3), so t holds four
+// 8-bit fields, each <= 16 (RC, both sets added first: <= 32); its even and odd fields go into
+// two int32 of two 16-bit fields: q[0] = bins 0 | 2, q[1] = bins 1 | 3 of the pass.
+struct GxPair {
+  uint32_t q[2];
+};
+__device__ __forceinline__ void gx_acc(int64_t &S, int t) { S += t; }
+__device__ __forceinline__ void gx_acc(GxPair &Q, int t) {
+  Q.q[0] += (uint32_t)t & 0x00FF00FFu;
+  Q.q[1] += ((uint32_t)t >> 8) & 0x00FF00FFu;
+}
+
 // NR rows' operands of one A block against the nbb staged blocks of one column; RC: against
 // both strands of the column, two accumulator sets (f forward, g reverse complement)
-template <int NR, bool TWO, bool RC>
+template <int NR, bool TWO, bool RC, typename ACC>
 __device__ __forceinline__ void gx_sweep(const GxLane<TWO> &L, const v4i (&a0)[NR],
                                          const v4i (&a1)[NR], const uint32_t *wcol,
                                          const uint32_t *vcol, int nbb, const int32_t *hm,
-                                         int64_t (&S)[NR]) {
+                                         ACC (&S)[NR]) {
   for (int bb = 0; bb < nbb; ++bb) {
     const uint32_t vw = __builtin_amdgcn_readfirstlane(vcol[bb]);
     if (vw == 0u) continue;
@@ -228,7 +260,7 @@ __device__ __forceinline__ void gx_sweep(const GxLane<TWO> &L, const v4i (&a0)[N
     if (vw != 0xFFFFFFFFu) gx_mask<TWO>(L, vw, b0, b1);
     if constexpr (!RC) {
 #pragma unroll
-      for (int r = 0; r < NR; ++r) S[r] += gx_lookup(hm, gx_mfma<TWO>(a0[r], a1[r], b0, b1));
+      for (int r = 0; r < NR; ++r) gx_acc(S[r], gx_lookup(hm, gx_mfma<TWO>(a0[r], a1[r], b0, b1)));
     } else {
       v4i c0, c1;
       gx_expand_left<TWO>(L, gx_pairrev32(w) ^ (0xFFFFFFFFu << L.lsh), c0, c1);
@@ -240,7 +272,7 @@ __device__ __forceinline__ void gx_sweep(const GxLane<TWO> &L, const v4i (&a0)[N
         int t = gx_lookup(hm, f);
         if (r + 1 < NR) f = gx_mfma<TWO>(a0[r + 1], a1[r + 1], b0, b1);  // ... under g's
         t += gx_lookup(hm, g);
-        S[r] += t;  // <= 32 adds of <= 12870 in the int32
+        gx_acc(S[r], t);  // <= 32 adds of <= 12870 in the int32
       }
     }
   }
@@ -305,11 +337,37 @@ __device__ __forceinline__ void gx_sweep_w(const GxLane<TWO> &L, const v4i (&a0)
   }
 }
 
-template <bool DIAG, bool TWO, bool RC, bool WT>
+// PF: what a profile launch counts and where it goes
+struct GxProf {
+  int d, pass;    // the bins 4 pass .. 4 pass + 3 of 0 .. d
+  int64_t *prof;  // [rows][ldp][d + 1] (DIAG: [n][d + 1]); nullptr: the filter in the epilogue
+  int64_t ldp;
+  double c[4];    // ... of one pass, d <= 3
+};
+
+// x = ((c[0] N_0 + c[1] N_1) + c[2] N_2) + ... up to m = d < NM, every product and sum rounded
+// on its own (a float64 host restatement gives the same bits); constant indices into c only
+template <int NM>
+__device__ __forceinline__ double gx_filter(const double (&c)[NM], const int64_t *N, int d) {
+  double x = __dmul_rn(c[0], (double)N[0]);
+#pragma unroll
+  for (int m = 1; m < NM; ++m)
+    if (m <= d) x = __dadd_rn(x, __dmul_rn(c[m], (double)N[m]));
+  return x;
+}
+
+__device__ __forceinline__ void gx_store(const OutSpec &o, int64_t at, double x, double s) {
+  if (o.normalize) x = x / s;
+  if (o.dtype == KMG_F64) ((double *)o.out)[at] = x;
+  else ((float *)o.out)[at] = (float)x;
+}
+
+template <bool DIAG, bool TWO, bool RC, bool WT, bool PF = false>
 __global__ __launch_bounds__(256, WT ? 2 : 1) void gram_gkmx_kernel(
     GkmxSide A, GkmxSide B, int l, int64_t row0, int64_t rows, int64_t tiles_c, GkmWeights wt,
     OutSpec o, const double *__restrict__ sa, const double *__restrict__ sb,
-    double *__restrict__ dsq_out) {
+    double *__restrict__ dsq_out, GxProf pf) {
+  static_assert(!(PF && WT), "a weighted field needs more bits than the profile's registers hold");
   constexpr int TRL = WT ? GX_WTR : GX_TR;            // tile rows the LDS holds
   __shared__ __align__(16) uint32_t wa[TRL][GX_CW];
   __shared__ __align__(16) uint32_t wb[GX_TC][GX_CW];
@@ -317,7 +375,7 @@ __global__ __launch_bounds__(256, WT ? 2 : 1) void gram_gkmx_kernel(
   __shared__ __align__(16) uint32_t ua[WT ? GX_WTR : 1][GX_CW / 4];  // WT: a weight byte a word
   __shared__ __align__(16) uint32_t ub[WT ? GX_TC : 1][GX_CW / 4];
   __shared__ int32_t hm[20];
-  __shared__ int64_t res[GX_TR][GX_TC];
+  __shared__ int64_t res[GX_TR][GX_TC][PF ? 4 : 1];
   constexpr int TRR = DIAG ? GX_TC : TRL;             // rows a tile
   constexpr int NRW = DIAG ? 1 : TRR / 4;             // rows of one sweep
   constexpr int NCW = DIAG ? 2 : GX_TC;               // sweeps' sums a wave
@@ -336,11 +394,21 @@ __global__ __launch_bounds__(256, WT ? 2 : 1) void gram_gkmx_kernel(
     nc = (int)min((int64_t)GX_TC, B.n - j0);
   }
 
-  // hm[m] = h[l - m] (constant indices into wt only: it stays in scalar registers)
+  if constexpr (PF) {
+    // hm[mm] = the counter of the bin m = l - mm where this pass counts it (0 < mm: the bin l of
+    // "no match" has no counter, so an all-zero operand still counts nothing), else 0
+    if (tid < 20) {
+      const int m = l - tid, b = m - 4 * pf.pass;
+      hm[tid] = (tid > 0 && m >= 0 && m <= pf.d && b >= 0 && b < 4) ? 1 << (8 * b) : 0;
+    }
+    for (int t = tid; t < GX_TR * GX_TC * 4; t += 256) (&res[0][0][0])[t] = 0;
+  } else {
+    // hm[m] = h[l - m] (constant indices into wt only: it stays in scalar registers)
 #pragma unroll
-  for (int d = 0; d < 17; ++d)
-    if (tid == l - d) hm[tid] = wt.h[d];
-  if (tid > l && tid < 20) hm[tid] = 0;
+    for (int d = 0; d < 17; ++d)
+      if (tid == l - d) hm[tid] = wt.h[d];
+    if (tid > l && tid < 20) hm[tid] = 0;
+  }
 
   GxLane<TWO> L;
   L.lr = lane & 31;
@@ -351,11 +419,11 @@ __global__ __launch_bounds__(256, WT ? 2 : 1) void gram_gkmx_kernel(
 #pragma unroll
   for (int q = 0; q < (TWO ? 8 : 4); ++q) L.val[q] = (8 * (q >> 2) + 4 * half + (q & 3)) < l ? 2u : 0u;
 
-  int64_t S[NCW][NRW];
+  typename std::conditional<PF, GxPair, int64_t>::type S[NCW][NRW];  // 64 VGPRs either way
 #pragma unroll
   for (int c = 0; c < NCW; ++c)
 #pragma unroll
-    for (int r = 0; r < NRW; ++r) S[c][r] = 0;
+    for (int r = 0; r < NRW; ++r) S[c][r] = {};
 
   const int nca = (A.nblk + GX_CB - 1) / GX_CB, ncb = (B.nblk + GX_CB - 1) / GX_CB;
   for (int ca = 0; ca < nca; ++ca) {
@@ -480,30 +548,83 @@ __global__ __launch_bounds__(256, WT ? 2 : 1) void gram_gkmx_kernel(
           }
         }
       }
+      if constexpr (PF) {
+        // the flush, once a chunk pair.  A lane's 16-bit field has gained at most GX_CB * GX_CB
+        // blocks * 16 entries * 2 (RC) = 2048 since the last one, so four xor-shuffle steps still
+        // fit it (16 lanes: 32768); then the fields are unpacked to 32 bits for the last two
+        // steps and lane 0 adds them to the pair's int64 bins.  Only the owning wave touches a
+        // pair's bins, so this needs neither atomics nor a barrier.
+        static_assert(GX_CB * GX_CB * 16 * 2 * 16 <= 65535, "a packed field overflows in the flush");
+        if ((DIAG ? 2 : NRW) * wave < nr) {  // wave-uniform
+#pragma unroll
+          for (int c = 0; c < NCW; ++c)
+#pragma unroll
+            for (int r = 0; r < NRW; ++r) {
+              uint32_t q0 = S[c][r].q[0], q1 = S[c][r].q[1];
+              S[c][r] = {};
+#pragma unroll
+              for (int d = 1; d <= 8; d <<= 1) {
+                q0 += __shfl_xor(q0, d, 64);
+                q1 += __shfl_xor(q1, d, 64);
+              }
+              uint32_t n[4] = {q0 & 0xFFFFu, q1 & 0xFFFFu, q0 >> 16, q1 >> 16};
+#pragma unroll
+              for (int b = 0; b < 4; ++b) {
+                n[b] += __shfl_xor(n[b], 16, 64);
+                n[b] += __shfl_xor(n[b], 32, 64);
+              }
+              if (lane == 0) {
+                int64_t *bins = DIAG ? res[2 * wave + c][0] : res[NRW * wave + r][c];
+#pragma unroll
+                for (int b = 0; b < 4; ++b) bins[b] += n[b];
+              }
+            }
+        }
+      }
     }
   }
 
   // one cross-lane reduction a pair
+  if constexpr (!PF) {
 #pragma unroll
-  for (int c = 0; c < NCW; ++c)
+    for (int c = 0; c < NCW; ++c)
 #pragma unroll
-    for (int r = 0; r < NRW; ++r) {
-      int64_t v = S[c][r];
+      for (int r = 0; r < NRW; ++r) {
+        int64_t v = S[c][r];
 #pragma unroll
-      for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-      if (lane == 0) {
-        if constexpr (DIAG) res[2 * wave + c][0] = v;
-        else res[NRW * wave + r][c] = v;
+        for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+        if (lane == 0) {
+          if constexpr (DIAG) res[2 * wave + c][0][0] = v;
+          else res[NRW * wave + r][c][0] = v;
+        }
       }
-    }
+  }
   __syncthreads();
 
+  if constexpr (PF) {
+    // the pass's bins into the stored profile, or (one pass, d <= 3) the filtered value
+    const int r = DIAG ? tid : tid / GX_TC, c = DIAG ? 0 : tid % GX_TC;
+    if (tid >= GX_TR * GX_TC || r >= nr || c >= nc) return;
+    const int64_t *N = res[r][c];
+    const int64_t at = DIAG ? i0 + r : (i0 - row0 + r) * (pf.prof ? pf.ldp : o.ld) + j0 + c;
+    if (pf.prof) {
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+        if (4 * pf.pass + b <= pf.d) pf.prof[at * (pf.d + 1) + 4 * pf.pass + b] = N[b];
+    } else {
+      const double x = gx_filter<4>(pf.c, N, pf.d);
+      if constexpr (DIAG) dsq_out[at] = __builtin_sqrt(x);
+      else gx_store(o, at, x, o.normalize ? sa[i0 + r] * sb[j0 + c] : 1.0);
+    }
+    return;
+  }
+
   if constexpr (DIAG) {
-    if (tid < nr) dsq_out[i0 + tid] = __builtin_sqrt((double)res[tid][0]);  // IEEE sqrt (RC: K2_ii)
+    if (tid < nr) dsq_out[i0 + tid] = __builtin_sqrt((double)res[tid][0][0]);  // IEEE sqrt (RC: K2_ii)
   } else {
     const int r = tid / GX_TC, c = tid % GX_TC;
     if (tid < GX_TR * GX_TC && r < nr && c < nc) {
-      const int64_t v = res[r][c];
+      const int64_t v = res[r][c][0];
       const int64_t at = (i0 - row0 + r) * o.ld + j0 + c;
       if (o.dtype == KMG_I32) {
         ((int32_t *)o.out)[at] = (int32_t)v;
@@ -527,7 +648,121 @@ auto gx_kernel(bool two, bool rc, bool wt) {
   return k[4 * two + 2 * rc + wt];
 }
 
+// ... of a profile launch (PF)
+template <bool DIAG>
+auto gx_kernel_pf(bool two, bool rc) {
+  decltype(&gram_gkmx_kernel<DIAG, false, false, false, true>) k[4] = {
+      gram_gkmx_kernel<DIAG, false, false, false, true>, gram_gkmx_kernel<DIAG, false, true, false, true>,
+      gram_gkmx_kernel<DIAG, true, false, false, true>,  gram_gkmx_kernel<DIAG, true, true, false, true>};
+  return k[2 * two + rc];
+}
+
+// sum_m c[m] N_m over a stored profile, one thread a pair
+__global__ __launch_bounds__(256) void gkm_filter_kernel(const int64_t *__restrict__ prof,
+                                                         int64_t rows, int64_t cols, int64_t ldp,
+                                                         int d, GkmFilter f, OutSpec o,
+                                                         const double *__restrict__ sa,
+                                                         const double *__restrict__ sb,
+                                                         double *__restrict__ dsq_out) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= rows * cols) return;
+  const int64_t i = t / cols, j = t - i * cols;
+  const double x = gx_filter<16>(f.c, prof + (i * ldp + j) * (d + 1), d);
+  if (dsq_out) dsq_out[i] = __builtin_sqrt(x);
+  else gx_store(o, i * o.ld + j, x, o.normalize ? sa[i] * sb[j] : 1.0);
+}
+
+// the passes of a profile launch (prof) or the one pass of a filtered one (f), rows split so
+// every launch stays below KMG_GKM_MAX_TILES tiles
+hipError_t gx_launch_pf(const GkmxSide &A, const GkmxSide &B, int l, int d, bool rc, int64_t row0,
+                        int64_t rows, int64_t *prof, int64_t ldp, const GkmFilter *f,
+                        const OutSpec &o, const double *sa, const double *sb, hipStream_t s) {
+  if (rows <= 0 || B.n <= 0) return hipSuccess;
+  if (l < 1 || l > 16 || d < 0 || d > l - 1 || A.nblk < 1 || B.nblk < 1 || A.wts || B.wts ||
+      row0 < 0 || row0 + rows > A.n)
+    return hipErrorInvalidValue;
+  if (prof ? ldp < B.n : (d > 3 || !o.out || o.ld < B.n || (o.normalize && (!sa || !sb))))
+    return hipErrorInvalidValue;
+  const int64_t tiles_c = (B.n + GX_TC - 1) / GX_TC;
+  if (tiles_c >= KMG_GKM_MAX_TILES) return hipErrorInvalidValue;  // AQL grid size is 32-bit
+  const int64_t max_rows = (KMG_GKM_MAX_TILES - 1) / tiles_c * GX_TR;
+  const size_t esz = o.dtype == KMG_F64 ? 8 : 4;
+  const auto kern = gx_kernel_pf<false>(l > 8, rc);
+  for (int pass = 0; 4 * pass <= d; ++pass)
+    for (int64_t r0 = 0; r0 < rows; r0 += max_rows) {
+      const int64_t nr = rows - r0 < max_rows ? rows - r0 : max_rows;
+      GxProf pf{d, pass, prof ? prof + r0 * ldp * (d + 1) : nullptr, ldp, {}};
+      for (int m = 0; f && m <= d; ++m) pf.c[m] = f->c[m];
+      OutSpec os = o;
+      if (!prof) os.out = (char *)o.out + (size_t)r0 * o.ld * esz;
+      hipLaunchKernelGGL(kern, dim3((unsigned)((nr + GX_TR - 1) / GX_TR * tiles_c)), dim3(256), 0, s,
+                         A, B, l, row0 + r0, nr, tiles_c, GkmWeights{}, os, sa, sb,
+                         (double *)nullptr, pf);
+      const hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return e;
+    }
+  return hipSuccess;
+}
+
+hipError_t gx_launch_pf_diag(const GkmxSide &A, int l, int d, bool rc, int64_t *prof,
+                             const GkmFilter *f, double *dsq, hipStream_t s) {
+  if (A.n <= 0) return hipSuccess;
+  if (l < 1 || l > 16 || d < 0 || d > l - 1 || A.nblk < 1 || A.wts) return hipErrorInvalidValue;
+  if (prof ? false : (d > 3 || !f || !dsq)) return hipErrorInvalidValue;
+  const int64_t tiles = (A.n + GX_TC - 1) / GX_TC;
+  if (tiles >= KMG_GKM_MAX_TILES) return hipErrorInvalidValue;
+  const auto kern = gx_kernel_pf<true>(l > 8, rc);
+  for (int pass = 0; 4 * pass <= d; ++pass) {
+    GxProf pf{d, pass, prof, 1, {}};
+    for (int m = 0; f && m <= d; ++m) pf.c[m] = f->c[m];
+    hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), 0, s, A, A, l, (int64_t)0, A.n,
+                       (int64_t)1, GkmWeights{}, OutSpec{}, (const double *)nullptr,
+                       (const double *)nullptr, dsq, pf);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 }  // namespace
+
+hipError_t launch_gkmx_profile(const GkmxSide &A, const GkmxSide &B, int l, int d, bool rc,
+                               int64_t row0, int64_t rows, int64_t *prof, int64_t ldp,
+                               hipStream_t s) {
+  if (!prof) return hipErrorInvalidValue;
+  return gx_launch_pf(A, B, l, d, rc, row0, rows, prof, ldp, nullptr, OutSpec{}, nullptr, nullptr, s);
+}
+
+hipError_t launch_gkmx_profile_diag(const GkmxSide &A, int l, int d, bool rc, int64_t *prof,
+                                    hipStream_t s) {
+  if (!prof) return hipErrorInvalidValue;
+  return gx_launch_pf_diag(A, l, d, rc, prof, nullptr, nullptr, s);
+}
+
+hipError_t launch_gkmx_filtered(const GkmxSide &A, const GkmxSide &B, int l, int d, bool rc,
+                                const GkmFilter &f, const OutSpec &o, const double *sa,
+                                const double *sb, hipStream_t s) {
+  return gx_launch_pf(A, B, l, d, rc, 0, A.n, nullptr, 0, &f, o, sa, sb, s);
+}
+
+hipError_t launch_gkmx_filtered_diag(const GkmxSide &A, int l, int d, bool rc, const GkmFilter &f,
+                                     double *dsq, hipStream_t s) {
+  return gx_launch_pf_diag(A, l, d, rc, nullptr, &f, dsq, s);
+}
+
+hipError_t launch_gkm_filter(const int64_t *prof, int64_t rows, int64_t cols, int64_t ldp, int d,
+                             const GkmFilter &f, const OutSpec &o, const double *sa,
+                             const double *sb, double *dsq, hipStream_t s) {
+  if (rows <= 0 || cols <= 0) return hipSuccess;
+  if (!prof || d < 0 || d > 15 || ldp < cols) return hipErrorInvalidValue;
+  if (dsq ? cols != 1 : (!o.out || o.ld < cols || (o.normalize && (!sa || !sb))))
+    return hipErrorInvalidValue;
+  const int64_t blocks = (rows * cols + 255) / 256;
+  if (blocks >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gkm_filter_kernel, dim3((unsigned)blocks), dim3(256), 0, s, prof, rows, cols,
+                     ldp, d, f, o, sa, sb, dsq);
+  return hipGetLastError();
+}
 
 hipError_t launch_gkmx_weights(const uint8_t *w, int64_t ldw, const int32_t *lens, int64_t n, int l,
                                int pmax, uint8_t *out, hipStream_t s) {
@@ -572,7 +807,7 @@ hipError_t launch_gram_gkmx(const GkmxSide &A, const GkmxSide &B, int l, bool rc
     OutSpec os = o;
     os.out = (char *)o.out + (size_t)r0 * o.ld * esz;
     hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, A, B, l, r0, rows, tiles_c, wt, os, sa, sb,
-                       (double *)nullptr);
+                       (double *)nullptr, GxProf{});
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
@@ -588,7 +823,8 @@ hipError_t launch_gkmx_diag(const GkmxSide &A, int l, bool rc, const GkmWeights 
   const OutSpec o{};
   const auto kern = gx_kernel<true>(l > 8, rc, A.wts != nullptr);
   hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), 0, s, A, A, l, (int64_t)0, A.n,
-                     (int64_t)1, wt, o, (const double *)nullptr, (const double *)nullptr, dsq);
+                     (int64_t)1, wt, o, (const double *)nullptr, (const double *)nullptr, dsq,
+                     GxProf{});
   return hipGetLastError();
 }
 

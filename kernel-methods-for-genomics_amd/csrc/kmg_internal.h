@@ -328,6 +328,37 @@ hipError_t launch_gram_gkmx(const GkmxSide &A, const GkmxSide &B, int l, bool rc
 hipError_t launch_gkmx_diag(const GkmxSide &A, int l, bool rc, const GkmWeights &wt, double *dsq,
                             hipStream_t s);
 
+// the mismatch profile N_m = #{(a, b) : ham(A_i word a, B_j word b) = m} (rc: + the same
+// against rc(B_j word b)), m = 0 .. d <= l - 1, from the PF instantiations of the same kernel:
+// the lookup table holds a packed counter a bin instead of a weight, four bins a pass,
+// ceil((d + 1) / 4) passes.  The bin m = l is not counted (an absent or invalid word matches
+// nowhere either): it is valid_a * valid_b (rc: twice that) less the other bins.  Sides with
+// weights are refused.
+struct GkmFilter {
+  double c[16];  // c[m] for m <= d, passed to the kernels by value
+};
+// rows [row0, row0 + rows) x all B.n columns: prof[((i - row0) * ldp + j) * (d + 1) + m]
+hipError_t launch_gkmx_profile(const GkmxSide &A, const GkmxSide &B, int l, int d, bool rc,
+                               int64_t row0, int64_t rows, int64_t *prof, int64_t ldp,
+                               hipStream_t s);
+// prof[i * (d + 1) + m] = N_m(A_i, A_i)
+hipError_t launch_gkmx_profile_diag(const GkmxSide &A, int l, int d, bool rc, int64_t *prof,
+                                    hipStream_t s);
+// d <= 3, one pass with the filter in the tile's epilogue:
+//   x = ((c[0] N_0 + c[1] N_1) + c[2] N_2) + c[3] N_3
+// every product and sum rounded on its own, at o.out (o.dtype KMG_F64 / KMG_F32; normalised:
+// x / (sa[i] * sb[j])); ... and dsq[i] = sqrt(x(A_i, A_i)) (IEEE: NaN where x < 0)
+hipError_t launch_gkmx_filtered(const GkmxSide &A, const GkmxSide &B, int l, int d, bool rc,
+                                const GkmFilter &f, const OutSpec &o, const double *sa,
+                                const double *sb, hipStream_t s);
+hipError_t launch_gkmx_filtered_diag(const GkmxSide &A, int l, int d, bool rc, const GkmFilter &f,
+                                     double *dsq, hipStream_t s);
+// the same expression, ascending in m up to any d <= 15, over a stored profile [rows][ldp][d + 1]:
+// out[i * o.ld + j] (normalised: / (sa[i] * sb[j])), or with dsq (cols = 1) dsq[i] = sqrt(x)
+hipError_t launch_gkm_filter(const int64_t *prof, int64_t rows, int64_t cols, int64_t ldp, int d,
+                             const GkmFilter &f, const OutSpec &o, const double *sa,
+                             const double *sb, double *dsq, hipStream_t s);
+
 // ---------------------------------------------------------------- scorer (kmg_score.hip)
 // V[key] = sum over the key's posting lists (exact index, copies = 1, every chunk) of the
 // 128-bit fixed-point weights fix[2 row], fix[2 row + 1] (low, high word), rounded once to

@@ -79,21 +79,24 @@ def get_gkm_K(X, l, k, d=None, *, both_strands=False):
     return _eng().gkm(_seqs(X), l, k, d, both_strands=both_strands)
 
 
-def get_gkm_cross_K(Xa, Xb, l, k, d=None, *, both_strands=False, center_weights=None):
+def get_gkm_cross_K(Xa, Xb, l, k=None, d=None, *, both_strands=False, center_weights=None,
+                    filter=None):
     """Gapped k-mer block K(Xa rows, Xb rows), normalised by both sides' own diagonals: the
     K(queries, support vectors) of gkm-SVM prediction, rows of any length.
     ``get_gkm_cross_K(X, X, ...)`` is the square gkm Gram of rows too long for ``get_gkm_K``
     (its diagonal is K_ii / (s_i s_i), 1 up to one rounding, not filled in).
     center_weights=(M, H): the centre-weighted kernel (LS-GKM's wgkm), every word weighted by
     ``params.gkm_center_weights(len(row), l, M, H)`` on both sides;
-    ``get_gkm_cross_K(X, X, ..., center_weights=(M, H))`` is the weighted square Gram."""
+    ``get_gkm_cross_K(X, X, ..., center_weights=(M, H))`` is the weighted square Gram.
+    filter=c: real coefficients c[0..d] on the mismatch profile in place of C(l - m, k)
+    (``GramEngine.gkm_cross(filter=)``; k may then be None; not together with center_weights)."""
     sa, sb = _seqs(Xa), _seqs(Xb)
     wa = wb = None
     if center_weights is not None:
         M, H = center_weights
         wa, wb = ([gkm_center_weights(len(s), l, M, H) for s in side] for side in (sa, sb))
     return _eng().gkm_cross(sa, sb, l, k, d, both_strands=both_strands, weights_a=wa,
-                            weights_b=wb)
+                            weights_b=wb, filter=filter)
 
 
 # ----------------------------------------------------------------------- helpers

@@ -40,6 +40,7 @@ EXPORTS = (
     "kmg_last_factorisation", "kmg_features_sym", "kmg_gram_device_cols",
     "kmg_scorer_create", "kmg_scorer_score", "kmg_scorer_score_device", "kmg_scorer_destroy",
     "kmg_gkm_cross", "kmg_gkm_cross_device", "kmg_gkm_cross_w", "kmg_gkm_cross_w_device",
+    "kmg_gkm_profile", "kmg_gkm_profile_device", "kmg_gkm_cross_f", "kmg_gkm_cross_f_device",
 )
 KMG_FEATURES_BCAST = 1
 KMG_FACTOR_CHOLESKY, KMG_FACTOR_LU_ASYMMETRIC, KMG_FACTOR_LU_INDEFINITE = 1, 2, 3
@@ -107,6 +108,14 @@ def load():
                                  I64, P, I64, I32, P, I64], ctypes.c_int),
             "kmg_gkm_cross_w_device": ([P, ctypes.POINTER(KmgParams), P, P, I64, I64, P, I64, P, P,
                                         I64, I64, P, I64, I32, P, I64], ctypes.c_int),
+            "kmg_gkm_profile": ([P, ctypes.POINTER(KmgParams), P, P, I64, I64, P, P, I64, I64, P,
+                                 I64], ctypes.c_int),
+            "kmg_gkm_profile_device": ([P, ctypes.POINTER(KmgParams), P, P, I64, I64, P, P, I64,
+                                        I64, P, I64], ctypes.c_int),
+            "kmg_gkm_cross_f": ([P, ctypes.POINTER(KmgParams), P, P, I64, I64, P, P, I64, I64, P,
+                                 I32, I32, P, I64], ctypes.c_int),
+            "kmg_gkm_cross_f_device": ([P, ctypes.POINTER(KmgParams), P, P, I64, I64, P, P, I64,
+                                        I64, P, I32, I32, P, I64], ctypes.c_int),
             "kmg_features": ([P, ctypes.POINTER(KmgParams), P, P, I64, I64, P, I64, P, I64],
                              ctypes.c_int),
             "kmg_features_sym": ([P, ctypes.POINTER(KmgParams), P, P, I64, I64, P, I64, I32, P,
@@ -260,16 +269,25 @@ class Context:
         return out
 
     def gkm_cross(self, params, codes_a, lens_a, codes_b, lens_b, out_dtype=KMG_F64,
-                  weights_a=None, weights_b=None):
+                  weights_a=None, weights_b=None, filter=None):
         """[na, nb] gapped k-mer block between the rows of A and of B, rows of any length
         (kmg_gkm_cross; params from ``params.gkm``).  weights_a / weights_b: uint8 [n, ldw]
-        position weights of a side's words (kmg_gkm_cross_w), None for all ones."""
+        position weights of a side's words (kmg_gkm_cross_w), None for all ones.  filter:
+        float64 [params.m + 1] coefficients of the mismatch profile (kmg_gkm_cross_f)."""
         codes_a = np.ascontiguousarray(codes_a, dtype=np.uint8)
         codes_b = np.ascontiguousarray(codes_b, dtype=np.uint8)
         lens_a = np.ascontiguousarray(lens_a, dtype=np.int32)
         lens_b = np.ascontiguousarray(lens_b, dtype=np.int32)
         (na, ldc_a), (nb, ldc_b) = codes_a.shape, codes_b.shape
         out = np.empty((na, nb), dtype=DTYPES[out_dtype])
+        if filter is not None:
+            if weights_a is not None or weights_b is not None:
+                raise KmgUnsupported(KMG_EUNSUPPORTED, "gkm cross: no position weights with a filter")
+            f = np.ascontiguousarray(filter, dtype=np.float64).reshape(-1)
+            check(self.lib.kmg_gkm_cross_f(self._h, ctypes.byref(params), ptr(codes_a),
+                                           ptr(lens_a), na, ldc_a, ptr(codes_b), ptr(lens_b), nb,
+                                           ldc_b, ptr(f), len(f), out_dtype, ptr(out), nb))
+            return out
         if weights_a is None and weights_b is None:
             check(self.lib.kmg_gkm_cross(self._h, ctypes.byref(params), ptr(codes_a), ptr(lens_a),
                                          na, ldc_a, ptr(codes_b), ptr(lens_b), nb, ldc_b,
@@ -282,6 +300,33 @@ class Context:
             0 if wa is None else wa.shape[1], ptr(codes_b), ptr(lens_b), nb, ldc_b, ptr(wb),
             0 if wb is None else wb.shape[1], out_dtype, ptr(out), nb))
         return out
+
+    def gkm_profile(self, params, codes_a, lens_a, codes_b, lens_b):
+        """int64 [na, nb, params.m + 1] mismatch profile N_m of every pair of rows
+        (kmg_gkm_profile)."""
+        codes_a = np.ascontiguousarray(codes_a, dtype=np.uint8)
+        codes_b = np.ascontiguousarray(codes_b, dtype=np.uint8)
+        lens_a = np.ascontiguousarray(lens_a, dtype=np.int32)
+        lens_b = np.ascontiguousarray(lens_b, dtype=np.int32)
+        (na, ldc_a), (nb, ldc_b) = codes_a.shape, codes_b.shape
+        out = np.empty((na, nb, params.m + 1), dtype=np.int64)
+        check(self.lib.kmg_gkm_profile(self._h, ctypes.byref(params), ptr(codes_a), ptr(lens_a), na,
+                                       ldc_a, ptr(codes_b), ptr(lens_b), nb, ldc_b, ptr(out), nb))
+        return out
+
+    def gkm_profile_device(self, params, d_codes_a, d_lens_a, na, ldc_a, d_codes_b, d_lens_b, nb,
+                           ldc_b, d_out, ld):
+        """The same on device pointers, on the context stream, without synchronising."""
+        check(self.lib.kmg_gkm_profile_device(self._h, ctypes.byref(params), d_codes_a, d_lens_a,
+                                              na, ldc_a, d_codes_b, d_lens_b, nb, ldc_b, d_out, ld))
+
+    def gkm_cross_f_device(self, params, d_codes_a, d_lens_a, na, ldc_a, d_codes_b, d_lens_b, nb,
+                           ldc_b, filter, out_dtype, d_out, ld):
+        """The filtered block on device pointers (kmg_gkm_cross_f_device; filter on the host)."""
+        f = np.ascontiguousarray(filter, dtype=np.float64).reshape(-1)
+        check(self.lib.kmg_gkm_cross_f_device(self._h, ctypes.byref(params), d_codes_a, d_lens_a,
+                                              na, ldc_a, d_codes_b, d_lens_b, nb, ldc_b, ptr(f),
+                                              len(f), out_dtype, d_out, ld))
 
     def gkm_cross_device(self, params, d_codes_a, d_lens_a, na, ldc_a, d_codes_b, d_lens_b, nb,
                          ldc_b, out_dtype, d_out, ld):

@@ -231,8 +231,23 @@ class GramEngine:
                                  "weight 0; its diagonal would be 0 under normalize=True")
         return out
 
-    def gkm_cross(self, seqs_a, seqs_b, l, k, d=None, normalize=True, out_dtype=L.KMG_F64, *,
-                  both_strands=False, weights_a=None, weights_b=None):
+    def gkm_profile(self, seqs_a, seqs_b, l, d, both_strands=False):
+        """int64 [len(seqs_a), len(seqs_b), d + 1] mismatch profile, the quantity under every
+        gkm kernel variant: N_m = #{(a, b) : ham(A_i[a:a+l], B_j[b:b+l]) = m} for m = 0..d,
+        0 <= d <= l - 1, with ``gkm_cross``'s word rules (kmg_gkm_profile: int8 MFMA, exact).
+        both_strands=True adds the counts against the reverse complement of B's words into the
+        same bins.  Any gkm kernel value at this l is a dot product with it: one profile serves
+        a model selection over (k, d) or a filter of the caller's."""
+        p = P.gkm_profile(l, d, both_strands)
+        seqs_a, seqs_b = list(seqs_a), list(seqs_b)
+        if not seqs_a or not seqs_b:
+            return np.zeros((len(seqs_a), len(seqs_b), int(d) + 1), dtype=np.int64)
+        codes_a, lens_a = E.encode(seqs_a)
+        codes_b, lens_b = E.encode(seqs_b)
+        return self.ctx.gkm_profile(p, codes_a, lens_a, codes_b, lens_b)
+
+    def gkm_cross(self, seqs_a, seqs_b, l, k=None, d=None, normalize=True, out_dtype=L.KMG_F64, *,
+                  both_strands=False, weights_a=None, weights_b=None, filter=None):
         """Rectangular gapped k-mer block [len(seqs_a), len(seqs_b)]:
         K_ij = sum_{a,b} h[ham(A_i[a:a+l], B_j[b:b+l])] with ``gkm``'s h and word rules, rows
         of any length, T^16 counted (kmg_gkm_cross: int8 MFMA).  This is K(queries, support
@@ -248,8 +263,32 @@ class GramEngine:
         weights, a reverse-complement word with the weight of the window it was made from, and
         the normalising diagonals with their own side's weights.  None is all ones.  Bad shapes
         or values and, under normalize=True, a row whose valid words all weigh 0 raise
-        ValueError before any device work."""
-        p = P.gkm(l, k, d, normalize, both_strands)
+        ValueError before any device work.
+        filter (kmg_gkm_cross_f): real coefficients c[0..d] in place of h, K_ij = sum_m c[m]
+        N_m(A_i, B_j) over the mismatch profile of ``gkm_profile``, summed in float64 in
+        ascending m, each product and sum rounded on its own; d = len(filter) - 1 <= l - 1 and k
+        may be None.  ``params.gkm_binomial_filter(l, k, d)`` gives the integer kernel back bit
+        for bit; the estimated l-mer filters of gkm-SVM 2.0 / LS-GKM are the caller's to supply.
+        Under normalize=True a filter with a non-positive diagonal gives inf / NaN there.  A
+        filter together with weights, an integer out_dtype or a d that disagrees with its length
+        raises ValueError."""
+        if filter is not None:
+            filter = np.asarray(filter, dtype=np.float64)
+            if weights_a is not None or weights_b is not None:
+                raise ValueError("gkm: filter= is not served together with position weights")
+            if filter.ndim != 1 or not 1 <= filter.shape[0] <= int(l):
+                raise ValueError(f"gkm: filter needs 1..l coefficients c[0..d], d <= l-1 (l={int(l)})")
+            if d is not None and int(d) != filter.shape[0] - 1:
+                raise ValueError(f"gkm: d={d} but the filter has {filter.shape[0]} coefficients")
+            if out_dtype == L.KMG_I32:
+                raise ValueError("gkm: a filtered block needs a floating dtype")
+            d = filter.shape[0] - 1
+            p = (P.gkm_profile(l, d, both_strands, normalize) if k is None
+                 else P.gkm(l, k, d, normalize, both_strands))
+        elif k is None:
+            raise ValueError("gkm: k is needed where no filter= is given")
+        else:
+            p = P.gkm(l, k, d, normalize, both_strands)
         seqs_a, seqs_b = list(seqs_a), list(seqs_b)
         wa = self._gkm_weights("a", weights_a, seqs_a, int(l), normalize)
         wb = self._gkm_weights("b", weights_b, seqs_b, int(l), normalize)
@@ -267,7 +306,7 @@ class GramEngine:
             return np.zeros((len(seqs_a), len(seqs_b)), dtype=L.DTYPES[out_dtype])
         codes_a, lens_a = E.encode(seqs_a)
         codes_b, lens_b = E.encode(seqs_b)
-        return self.ctx.gkm_cross(p, codes_a, lens_a, codes_b, lens_b, out_dtype, wa, wb)
+        return self.ctx.gkm_cross(p, codes_a, lens_a, codes_b, lens_b, out_dtype, wa, wb, filter)
 
     # ------------------------------------------------------------------ scoring
     def scorer(self, method, seqs, coef):

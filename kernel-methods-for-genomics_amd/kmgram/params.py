@@ -60,6 +60,30 @@ def gkm(l, k, d=None, normalize=True, both_strands=False):
                 strands=2 if both_strands else 0)
 
 
+def gkm_profile(l, d, both_strands=False, normalize=False):
+    """KmgParams of a mismatch-profile or filtered gkm call: word length l (1..16), bins
+    m = 0..d (0 <= d <= l - 1).  No k enters: the struct carries k = l, m = d and g = d, the
+    least the gkm parameter rule (g >= m) lets through."""
+    l, d = int(l), int(d)
+    if not 1 <= l <= 16:
+        raise ValueError(f"gkm: word length l={l} outside 1..16")
+    if not 0 <= d <= l - 1:
+        raise ValueError(f"gkm: profile truncation d={d} outside 0..l-1 (l={l})")
+    return make(L.KMG_GKM, k=l, g=d, m=d, normalize=1 if normalize else 0,
+                strands=2 if both_strands else 0)
+
+
+def gkm_binomial_filter(l, k, d):
+    """float64 [d + 1]: C(l - m, k) for m = 0..d, the filter under which
+    ``GramEngine.gkm_cross(filter=)`` equals the integer gkm kernel of (l, k, d) bit for bit.
+    The estimated l-mer filters of gkm-SVM 2.0 / LS-GKM (truncated, full) have no closed form
+    shipped here -- they could not be pinned against those programs -- so the caller supplies
+    such coefficients."""
+    import numpy as np
+    gkm(l, k, d)  # the parameter rules
+    return np.array(gkm_weights(int(l), int(k), int(d))[:int(d) + 1], dtype=np.float64)
+
+
 def gkm_center_weights(length, l, M=50, H=50):
     """uint8 position weights of the words a = 0 .. length - l of a row of ``length`` letters,
     for the weighted gkm kernel (``GramEngine.gkm_cross(weights_a=, weights_b=)``):
