@@ -327,9 +327,59 @@ int kmg_scorer_score(kmg_ctx *ctx, const kmg_scorer *s, const uint8_t *codes, co
 int kmg_scorer_score_device(kmg_ctx *ctx, const kmg_scorer *s, const uint8_t *d_codes,
                             const int32_t *d_lens, int64_t nq, int64_t ldc, double bias,
                             double *d_out);
-/* Frees the table of a scorer of KRR.py:43-56 / SVM.py:99-111 (after the stream drains).
+/* Frees the table of a scorer of KRR.py:43-56 / SVM.py:99-111 (after the stream drains), of
+ * either kind (kmg_scorer_create, kmg_gkm_scorer_create).
  * ctx may be NULL when the context was destroyed first; the table is freed all the same. */
 int kmg_scorer_destroy(kmg_ctx *ctx, kmg_scorer *s);
+
+/*
+ * The gapped k-mer model as one table (gkm-SVM's gkmpredict and its l-mer weight export):
+ * the gkm kernels are inner products of explicit feature maps over the 4^l words, so
+ *   f(q) = sum_t coef[t] K(q, x_t) + bias = sum_a u_q[a] U[q word a] (/ sqrt(K_qq)) + bias
+ *   U[z] = sum_{m <= d} c[m] sum_{v : ham(z, v) = m} V[v]
+ *   V[v] = sum_t beta_t sum_b w_t[b] ([x_t word b = v] + [strands = 2] [rc(x_t word b) = v])
+ * with K the kernel of kmg_gkm_cross (filter = NULL: c[m] = C(l - m, k) from p), of
+ * kmg_gkm_cross_f (c[m] = filter[m], nfilter = p->m + 1, else KMG_EINVAL), of kmg_gkm_cross_w
+ * (wts: uint8 [n][ldw] position weights, word b of row t at [t][b], ldw at least the longest
+ * row's word count, else KMG_EINVAL; NULL: ones) or of a filter and weights together, raw,
+ * which no block entry point serves.  beta_t = coef[t], or coef[t] / sqrt(K_tt) under
+ * p->normalize = 1, the diagonals from the DIAG form of the same kmg_gkm_cross* call (that form
+ * has no weighted filter: normalize = 1 with wts and a filter is KMG_EUNSUPPORTED; a training
+ * row whose diagonal is not positive while its coef is not 0 is KMG_EINVAL).  Word rules, row
+ * lengths and p as in kmg_gkm_cross; p->strands = 2 is kmg_gkm_cross's: Hamming distance is
+ * invariant under reverse complement, so V alone is symmetrised.
+ *   Supported: 1 <= l <= 12, d <= 4 (five tables of 4^l doubles in the workspace while the
+ *   model is built); l > 12, d > 4 or a filter of more than five bins is KMG_EUNSUPPORTED, as is
+ *   a kind other than KMG_GKM and 2^36 or more training words; a non-finite coef or filter
+ *   entry is KMG_EINVAL.  All of it is checked before any allocation or launch.
+ *   Reproducible: every coef enters V as a 128-bit fixed-point integer (80 fraction bits below
+ *   the binade of max |beta|; 2 strands * 255 * 2^36 words * 2^80 < 2^127) added with integer
+ *   atomics, exact in any order, and is rounded to double once; everything after adds doubles
+ *   in an order fixed by the launch geometry, which follows from ldc alone.  Two scorers built
+ *   from the same inputs hold byte-identical tables and give byte-identical scores.
+ * Host buffers, synchronous.  Stages "vtab", "butterfly" (and "diag" under normalisation).
+ */
+int kmg_gkm_scorer_create(kmg_ctx *ctx, const kmg_params *p, const uint8_t *codes,
+                          const int32_t *lens, int64_t n, int64_t ldc, const uint8_t *wts,
+                          int64_t ldw, const double *coef, const double *filter, int32_t nfilter,
+                          kmg_scorer **out);
+/* gkmpredict: out[q] = f(q) for nq host rows of any length, wts their position weights (uint8
+ * [nq][ldw], NULL: ones; with a normalised, filtered model KMG_EUNSUPPORTED).  A query without
+ * a valid word scores bias, or NaN under normalisation (0 / 0, as the Gram epilogue gives).  A
+ * scorer of kmg_scorer_create is KMG_EINVAL here, and a gkm scorer in kmg_scorer_score*.
+ * Synchronous.  Stages "score" (and "diag"). */
+int kmg_gkm_scorer_score(kmg_ctx *ctx, const kmg_scorer *s, const uint8_t *codes,
+                         const int32_t *lens, int64_t nq, int64_t ldc, const uint8_t *wts,
+                         int64_t ldw, double bias, double *out);
+/* gkmpredict on device pointers (rows up to ldc symbols bound the checks, ldw included): runs
+ * on the context stream and returns without synchronising.  Same bits as the host form. */
+int kmg_gkm_scorer_score_device(kmg_ctx *ctx, const kmg_scorer *s, const uint8_t *d_codes,
+                                const int32_t *d_lens, int64_t nq, int64_t ldc,
+                                const uint8_t *d_wts, int64_t ldw, double bias, double *d_out);
+/* The l-mer weights of gkm-SVM (deltaSVM's input): out[z] = U[z] for all 4^l words, word z
+ * indexed as the library codes words (base 4, A C G T = 0 1 2 3, first letter most
+ * significant).  Under strands = 2, out[z] and out[rc(z)] hold the same bits.  Synchronous. */
+int kmg_gkm_scorer_table(kmg_ctx *ctx, const kmg_scorer *s, double *out);
 
 /*
  * The full K of all n rows into HOST memory h_out (row stride ld_host elements; e.g. a

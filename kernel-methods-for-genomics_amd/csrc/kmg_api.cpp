@@ -169,6 +169,8 @@ struct Tuning {
   int gkm_prof_ws = 256;    // KMG_GKM_PROF_WS: MB of profile workspace a row slab of kmg_gkm_cross_f
                             // may take where the filter has more than four bins (a slab is one
                             // 16-row tile at the least: 0 gives 16-row slabs)
+  int gkm_score_g = 0;      // KMG_GKM_SCORE_G: lanes a query of the gkm table scorer, 8 / 16 / 64 /
+                            // 256 (0 auto: from the row bound, gkm_score_lanes; timing runs only)
   int check = 0;            // KMG_CHECK: 1 validate the neighbourhood lists' metadata after
                             // every fill (nb_check_kernel; one host sync a build) and fail with
                             // KMG_EINTERNAL before any Gram launch reads past a list; 2 the
@@ -216,6 +218,7 @@ void read_tuning(Tuning &t) {
   t.dense_bk = env_or("KMG_DENSE_BK", d.dense_bk);
   t.dense_half = env_or("KMG_DENSE_HALF", d.dense_half);
   t.gkm_prof_ws = std::max(0, std::min(65536, env_or("KMG_GKM_PROF_WS", d.gkm_prof_ws)));
+  t.gkm_score_g = env_or("KMG_GKM_SCORE_G", d.gkm_score_g);
   t.check = env_or("KMG_CHECK", d.check);
   if (getenv("KMG_MM_CHUNK") == nullptr) t.mm_chunk = 0;  // 0: per-formulation default
 }
@@ -247,6 +250,7 @@ struct kmg_ctx {
   DevBuf chk;                       // KMG_CHECK: validation flag + first offending list
   DevBuf cb_scratch;                // column-block assembly: one rank's K[:, C_q] (n x block)
   DevBuf sc_fix, sc_tab;            // kmg_scorer_create: fixed-point weights, the DP tables
+  DevBuf sc_acc;                    // kmg_gkm_scorer_create: the 128-bit integer table
   DevBuf gx_words_b, gx_bits;       // kmg_gkm_cross: side B's words (side A's are in kmers),
                                     // the validity bits of A, then B
   DevBuf gx_wts, gx_wts_in;         // kmg_gkm_cross_w: the laid-out weights of A, then B; the
@@ -1667,7 +1671,7 @@ int kmg_destroy(kmg_ctx *c) {
                     &c->tri_stage, &c->tri_scratch, &c->dense_tiles, &c->ovf, &c->slabs,
                     &c->gcoef, &c->feat32, &c->k32, &c->ft_cols,
                     &c->nb_seg, &c->nb_use, &c->nb_lines, &c->chk, &c->cb_scratch,
-                    &c->sc_fix, &c->sc_tab, &c->gx_words_b, &c->gx_bits, &c->gx_prof};
+                    &c->sc_fix, &c->sc_tab, &c->sc_acc, &c->gx_words_b, &c->gx_bits, &c->gx_prof};
   for (DevBuf *b : bufs) b->release();
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
   if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
@@ -2228,6 +2232,11 @@ struct kmg_scorer {
   int maxd = 0;            // largest Hamming distance with a non-zero weight
   int64_t w[33] = {};      // mismatch_weights (spectrum: 1, 0, ...)
   DevBuf U, wtab;          // 4^k doubles; the weights on the device (the queries' diagonal)
+  // kmg_gkm_scorer_create (kind KMG_GKM; k = l): the parameters and weights of the diagonals
+  kmg_params gp = {};
+  GkmWeights gh = {};
+  GkmFilter gf = {};
+  bool has_filter = false;
 };
 
 static int scorer_check_params(const kmg_params *p) {
@@ -2447,6 +2456,7 @@ int kmg_scorer_score_device(kmg_ctx *c, const kmg_scorer *s, const uint8_t *d_co
                             const int32_t *d_lens, int64_t nq, int64_t ldc, double bias,
                             double *d_out) {
   if (!c || !s) return fail(KMG_EINVAL, "ctx / scorer is NULL");
+  if (s->kind == KMG_GKM) return fail(KMG_EINVAL, "a gkm scorer is scored by kmg_gkm_scorer_score*");
   std::lock_guard<std::mutex> lk(c->mu);
   if (nq < 0 || ldc <= 0) return fail(KMG_EINVAL, "bad shape");
   if (nq > 0 && (!d_codes || !d_lens || !d_out)) return fail(KMG_EINVAL, "NULL buffer");
@@ -2457,6 +2467,7 @@ int kmg_scorer_score_device(kmg_ctx *c, const kmg_scorer *s, const uint8_t *d_co
 int kmg_scorer_score(kmg_ctx *c, const kmg_scorer *s, const uint8_t *codes, const int32_t *lens,
                      int64_t nq, int64_t ldc, double bias, double *out) {
   if (!c || !s) return fail(KMG_EINVAL, "ctx / scorer is NULL");
+  if (s->kind == KMG_GKM) return fail(KMG_EINVAL, "a gkm scorer is scored by kmg_gkm_scorer_score*");
   std::lock_guard<std::mutex> lk(c->mu);
   int maxlen = 0;
   KMG_TRY(scorer_check_rows(s->kind, s->window, codes, lens, nq, ldc, &maxlen));
@@ -2471,6 +2482,316 @@ int kmg_scorer_score(kmg_ctx *c, const kmg_scorer *s, const uint8_t *codes, cons
   KMG_TRY(scorer_score_device(c, s, c->h_codes.as<uint8_t>(), c->h_lens.as<int32_t>(), nq, ldc,
                               bias, c->h_out.as<double>()));
   KMG_HIP(hipMemcpyAsync(out, c->h_out.p, sizeof(double) * nq, hipMemcpyDeviceToHost, c->stream));
+  KMG_HIP(hipStreamSynchronize(c->stream));
+  return KMG_OK;
+}
+
+// ----------------------------------------------------------------- gkm table scorer
+// sqrt(K_ii) of n device rows into dq by the DIAG form of kmg_gkm_cross* (f = nullptr: the
+// weights wt, position weights allowed), or of kmg_gkm_cross_f* (the filter f, no position
+// weights); the rows' records are in pk already
+static int gkm_scorer_diag(kmg_ctx *c, const kmg_scorer *s, const Packed &pk, const int32_t *d_lens,
+                           int64_t n, int pmax, const uint8_t *d_w, int64_t ldw, double *dq) {
+  const int l = s->k, d = s->m;
+  const bool rc = s->gp.strands == 2;
+  const int nblk = gkmx_blocks(pmax);
+  KMG_TRY(c->kmers.ensure(sizeof(uint32_t) * (size_t)n * nblk * 32));
+  KMG_TRY(c->gx_bits.ensure(sizeof(uint32_t) * (size_t)n * nblk));
+  GkmxSide A{c->kmers.as<uint32_t>(), c->gx_bits.as<uint32_t>(), n, nblk};
+  if (d_w) {
+    KMG_TRY(c->gx_wts.ensure((size_t)n * nblk * 32));
+    A.wts = c->gx_wts.as<uint8_t>();
+  }
+  if (s->has_filter && d > 3) KMG_TRY(c->gx_prof.ensure(sizeof(int64_t) * (size_t)n * (d + 1)));
+  {
+    StageTimer t(c, ST_EXTRACT);
+    KMG_HIP(launch_gkmx_extract(pk, n, l, pmax, c->kmers.as<uint32_t>(), c->gx_bits.as<uint32_t>(),
+                                c->stream));
+    if (d_w)
+      KMG_HIP(launch_gkmx_weights(d_w, ldw, d_lens, n, l, pmax, c->gx_wts.as<uint8_t>(), c->stream));
+  }
+  StageTimer t(c, ST_DIAG);
+  if (!s->has_filter) {
+    KMG_HIP(launch_gkmx_diag(A, l, rc, s->gh, dq, c->stream));
+  } else if (d <= 3) {
+    KMG_HIP(launch_gkmx_filtered_diag(A, l, d, rc, s->gf, dq, c->stream));
+  } else {
+    int64_t *prof = c->gx_prof.as<int64_t>();
+    KMG_HIP(launch_gkmx_profile_diag(A, l, d, rc, prof, c->stream));
+    KMG_HIP(launch_gkm_filter(prof, n, 1, 1, d, s->gf, OutSpec{}, nullptr, nullptr, dq, c->stream));
+  }
+  return KMG_OK;
+}
+
+// host rows of either gkm scorer call: lens inside [0, ldc], the longest row, the words of all
+static int gkm_scorer_rows(const uint8_t *codes, const int32_t *lens, int64_t n, int64_t ldc, int l,
+                           int *maxlen, int64_t *words) {
+  if (n < 0 || ldc <= 0) return fail(KMG_EINVAL, "bad shape");
+  if (n > 0 && (!codes || !lens)) return fail(KMG_EINVAL, "NULL buffer");
+  *maxlen = 0;
+  *words = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    if (lens[i] < 0 || lens[i] > ldc) return fail(KMG_EINVAL, "lens[%lld] outside [0,ldc]", (long long)i);
+    *maxlen = std::max(*maxlen, (int)lens[i]);
+    *words += std::max(0, (int)lens[i] - l + 1);
+  }
+  return KMG_OK;
+}
+
+// the diagonals' bounds of kmg_gkm_cross* (w: the side is weighted), as those calls check them
+static int gkm_scorer_diag_bounds(const kmg_scorer *s, int maxlen, int64_t n, bool w) {
+  const GkmPfCall pf{&s->gf};
+  return gkm_cross_bounds(&s->gp, s->gh, maxlen, n, maxlen, n, KMG_F64, w ? 255 : 1, w ? 255 : 1,
+                          s->has_filter ? &pf : nullptr);
+}
+
+int kmg_gkm_scorer_create(kmg_ctx *c, const kmg_params *p, const uint8_t *codes,
+                          const int32_t *lens, int64_t n, int64_t ldc, const uint8_t *wts,
+                          int64_t ldw, const double *coef, const double *filter, int32_t nfilter,
+                          kmg_scorer **out) {
+  if (!c) return fail(KMG_EINVAL, "ctx is NULL");
+  if (!out) return fail(KMG_EINVAL, "out is NULL");
+  *out = nullptr;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!p) return fail(KMG_EINVAL, "params is NULL");
+  if (p->kind != KMG_GKM)
+    return fail(KMG_EUNSUPPORTED, "gkm scorer: kernel kind %d is not KMG_GKM", p->kind);
+  std::unique_ptr<kmg_scorer> s(new kmg_scorer());
+  KMG_TRY(gkm_check(p, KMG_F64, s->gh));
+  if (p->normalize != 0 && p->normalize != 1) return fail(KMG_EINVAL, "normalize must be 0 or 1");
+  const int l = p->k, d = p->m;
+  const bool rc = p->strands == 2;
+  if (l > 12) return fail(KMG_EUNSUPPORTED, "gkm scorer: 1 <= l <= 12 (l = %d)", l);
+  if (d > 4 || (filter && nfilter > 5))
+    return fail(KMG_EUNSUPPORTED, "gkm scorer: at most five bins, d <= 4 (d = %d, filter of %d)", d,
+                filter ? (int)nfilter : d + 1);
+  if (filter && nfilter != d + 1)
+    return fail(KMG_EINVAL, "gkm scorer: a filter of %d coefficients for m = 0..%d", nfilter, d);
+  if (p->normalize && wts && filter)
+    return fail(KMG_EUNSUPPORTED, "gkm scorer: normalize = 1 is not served with position weights "
+                "and a filter together (no weighted filtered diagonal)");
+  if (n < 1 || !coef) return fail(KMG_EINVAL, "gkm scorer: no training rows / coef is NULL");
+  int maxlen = 0;
+  int64_t words = 0;
+  KMG_TRY(gkm_scorer_rows(codes, lens, n, ldc, l, &maxlen, &words));
+  if (words >= KMG_GKS_MAX_WORDS)
+    return fail(KMG_EUNSUPPORTED, "gkm scorer: %lld training words are past the 2^36 of the "
+                "fixed-point table", (long long)words);
+  const int P = std::max(0, maxlen - l + 1);
+  if (wts && ldw < P)
+    return fail(KMG_EINVAL, "gkm scorer: ldw = %lld is less than the %d words of the longest row",
+                (long long)ldw, P);
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(coef[i])) return fail(KMG_EINVAL, "coef[%lld] is not finite", (long long)i);
+  for (int m = 0; filter && m <= d; ++m)
+    if (!std::isfinite(filter[m])) return fail(KMG_EINVAL, "filter[%d] is not finite", m);
+  s->kind = KMG_GKM;
+  s->device = c->device;
+  s->k = l;
+  s->m = d;
+  s->gp = *p;
+  s->norm = p->normalize != 0;
+  s->has_filter = filter != nullptr;
+  double cm[5] = {0, 0, 0, 0, 0};
+  for (int m = 0; m <= d; ++m) {
+    cm[m] = filter ? filter[m] : (double)s->gh.h[m];
+    s->gf.c[m] = cm[m];
+  }
+  if (s->norm) KMG_TRY(gkm_scorer_diag_bounds(s.get(), maxlen, n, wts != nullptr));
+  KMG_HIP(hipSetDevice(c->device));
+  c->last_call_first = (int)c->ev_log.size();
+  struct Release {  // a failed create leaves nothing behind
+    kmg_scorer *s;
+    ~Release() {
+      if (s) s->U.release();
+    }
+  } guard{s.get()};
+
+  const int64_t nkeys = pow4(l);
+  const int nt = d + 1;
+  const int cw = packed_cw(ldc), mw = packed_mw(ldc);
+  KMG_TRY(c->h_codes.ensure((size_t)n * ldc));
+  KMG_TRY(c->h_lens.ensure(sizeof(int32_t) * (size_t)n));
+  KMG_TRY(c->packed.ensure(sizeof(uint32_t) * (size_t)n * (cw + mw)));
+  KMG_TRY(s->U.ensure(sizeof(double) * (size_t)nkeys));
+  KMG_TRY(c->sc_tab.ensure(sizeof(double) * (size_t)nt * (size_t)nkeys));
+  KMG_TRY(c->sc_acc.ensure(sizeof(uint64_t) * 2 * (size_t)nkeys));
+  KMG_TRY(c->sc_fix.ensure(sizeof(uint64_t) * 2 * (size_t)n));
+  KMG_HIP(hipMemcpyAsync(c->h_codes.p, codes, (size_t)n * ldc, hipMemcpyHostToDevice, c->stream));
+  KMG_HIP(hipMemcpyAsync(c->h_lens.p, lens, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
+  const uint8_t *d_w = nullptr;
+  if (wts) {
+    KMG_TRY(c->gx_wts_in.ensure(std::max<size_t>((size_t)n * ldw, 16)));
+    if (n * ldw > 0)
+      KMG_HIP(hipMemcpyAsync(c->gx_wts_in.p, wts, (size_t)n * ldw, hipMemcpyHostToDevice, c->stream));
+    d_w = c->gx_wts_in.as<uint8_t>();
+  }
+  const Packed pk{c->packed.as<uint32_t>(), (int64_t)(cw + mw), cw};
+  {
+    StageTimer t(c, ST_PACK);
+    KMG_HIP(launch_pack(c->h_codes.as<uint8_t>(), c->h_lens.as<int32_t>(), n, ldc, 0,
+                        c->packed.as<uint32_t>(), c->stream));
+  }
+  // beta_t = coef_t, or coef_t / sqrt(K_tt) with the diagonal of the kernel that is scored
+  std::vector<double> beta(coef, coef + n);
+  if (s->norm) {
+    KMG_TRY(c->dsq.ensure(sizeof(double) * (size_t)n));
+    KMG_TRY(gkm_scorer_diag(c, s.get(), pk, c->h_lens.as<int32_t>(), n, std::max(1, P), d_w, ldw,
+                            c->dsq.as<double>()));
+    std::vector<double> dsq((size_t)n);
+    KMG_HIP(hipMemcpyAsync(dsq.data(), c->dsq.p, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    KMG_HIP(hipStreamSynchronize(c->stream));
+    for (int64_t i = 0; i < n; ++i) {
+      if (beta[i] == 0.0) continue;
+      if (!(dsq[i] > 0.0))
+        return fail(KMG_EINVAL, "gkm scorer: training row %lld has no positive diagonal (no valid "
+                    "word, zero weights or the filter), its normalised kernel row is undefined",
+                    (long long)i);
+      beta[i] /= dsq[i];
+    }
+  }
+  // 128-bit fixed point, KMG_GKS_FRAC fraction bits below 2^E > max |beta| (kmg_score.hip (4))
+  double bmax = 0.0;
+  for (double b : beta) bmax = std::max(bmax, std::fabs(b));
+  int E = 0;
+  if (bmax > 0.0) (void)std::frexp(bmax, &E);
+  std::vector<uint64_t> fix((size_t)2 * n);
+  for (int64_t i = 0; i < n; ++i) {
+    // the magnitude first (hi and lo are exact for a non-negative double), then the two's
+    // complement of the 128-bit integer for a negative beta, as kmg_scorer_create does
+    const double ax = std::ldexp(std::fabs(beta[i]), KMG_GKS_FRAC - E);
+    const double hid = std::floor(std::ldexp(ax, -64));
+    uint64_t lo = (uint64_t)(ax - std::ldexp(hid, 64)), hi = (uint64_t)hid;
+    if (beta[i] < 0.0) {
+      lo = ~lo + 1;
+      hi = ~hi + (lo == 0 ? 1 : 0);
+    }
+    fix[2 * i] = lo;
+    fix[2 * i + 1] = hi;
+  }
+  KMG_HIP(hipMemcpyAsync(c->sc_fix.p, fix.data(), sizeof(uint64_t) * fix.size(),
+                         hipMemcpyHostToDevice, c->stream));
+  double *T = c->sc_tab.as<double>();
+  {
+    StageTimer t(c, ST_VTAB);
+    KMG_HIP(launch_gkm_vtab(pk, mw, n, l, P, d_w, ldw, c->sc_fix.as<uint64_t>(),
+                            c->sc_acc.as<uint64_t>(), c->stream));
+    KMG_HIP(launch_gkm_vconv(c->sc_acc.as<uint64_t>(), l, rc, E - KMG_GKS_FRAC, T, c->stream));
+  }
+  {
+    int hb = 16;
+    const int t = score_tile_digits(nt, (size_t)c->lds_max, &hb);
+    StageTimer tm(c, ST_BUTTERFLY);
+    for (int lo = 0; lo < l; lo += t) {
+      const int tg = std::min(t, l - lo);
+      const bool last = nt == 1 || lo + tg >= l;
+      KMG_HIP(launch_score_butterfly(T, l, nt, lo, tg, hb, lo == 0, last, cm, s->U.as<double>(),
+                                     c->stream));
+      if (last) break;
+    }
+    if (rc) KMG_HIP(launch_gkm_usym(s->U.as<double>(), l, c->stream));
+  }
+  KMG_HIP(hipStreamSynchronize(c->stream));  // pageable sources; U is complete on return
+  guard.s = nullptr;
+  *out = s.release();
+  return KMG_OK;
+}
+
+// queries on the device -> d_out on the context stream (no lock, no synchronise); maxlen
+// bounds the rows (ldc in the device form) and the lanes a query follow from ldc alone
+static int gkm_scorer_score_device(kmg_ctx *c, const kmg_scorer *s, const uint8_t *d_codes,
+                                   const int32_t *d_lens, int64_t nq, int64_t ldc, int maxlen,
+                                   const uint8_t *d_wts, int64_t ldw, double bias, double *d_out) {
+  c->last_call_first = (int)c->ev_log.size();
+  const int l = s->k;
+  const int P = std::max(0, maxlen - l + 1), Pg = std::max(0, (int)ldc - l + 1);
+  const int cw = packed_cw(ldc), mw = packed_mw(ldc);
+  KMG_TRY(c->packed.ensure(sizeof(uint32_t) * (size_t)nq * (cw + mw)));
+  const Packed pk{c->packed.as<uint32_t>(), (int64_t)(cw + mw), cw};
+  {
+    StageTimer t(c, ST_PACK);
+    KMG_HIP(launch_pack(d_codes, d_lens, nq, ldc, 0, c->packed.as<uint32_t>(), c->stream));
+  }
+  if (s->norm) {  // sqrt(K_qq) of every query
+    KMG_TRY(c->dsq.ensure(sizeof(double) * (size_t)nq));
+    KMG_TRY(gkm_scorer_diag(c, s, pk, d_lens, nq, std::max(1, P), d_wts, ldw, c->dsq.as<double>()));
+  }
+  int G = gkm_score_lanes(Pg);
+  const int tg = c->tune.gkm_score_g;
+  if ((tg == 8 || tg == 16 || tg == 64 || tg == 256) && (tg == 256 || Pg <= 1024)) G = tg;
+  StageTimer t(c, ST_SCORE);
+  KMG_HIP(launch_gkm_score(pk, mw, nq, l, P, G, d_wts, ldw, s->U.as<double>(),
+                           s->norm ? c->dsq.as<double>() : nullptr, bias, d_out, c->stream));
+  return KMG_OK;
+}
+
+// what both forms check before anything is allocated or launched
+static int gkm_scorer_score_check(const kmg_scorer *s, int64_t nq, int maxlen, const uint8_t *wts,
+                                  int64_t ldw) {
+  if (s->kind != KMG_GKM)
+    return fail(KMG_EINVAL, "gkm scorer: the scorer was made by kmg_scorer_create");
+  if (s->norm && s->has_filter && wts)
+    return fail(KMG_EUNSUPPORTED, "gkm scorer: a normalised, filtered model takes no position "
+                "weights (no weighted filtered diagonal)");
+  if (wts && ldw < std::max(0, maxlen - s->k + 1))
+    return fail(KMG_EINVAL, "gkm scorer: ldw = %lld is less than the %d words of the longest row",
+                (long long)ldw, std::max(0, maxlen - s->k + 1));
+  if (s->norm) KMG_TRY(gkm_scorer_diag_bounds(s, maxlen, nq, wts != nullptr));
+  return KMG_OK;
+}
+
+int kmg_gkm_scorer_score_device(kmg_ctx *c, const kmg_scorer *s, const uint8_t *d_codes,
+                                const int32_t *d_lens, int64_t nq, int64_t ldc,
+                                const uint8_t *d_wts, int64_t ldw, double bias, double *d_out) {
+  if (!c || !s) return fail(KMG_EINVAL, "ctx / scorer is NULL");
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (nq < 0 || ldc <= 0) return fail(KMG_EINVAL, "bad shape");
+  KMG_TRY(gkm_scorer_score_check(s, nq, (int)ldc, d_wts, ldw));
+  if (nq == 0) return KMG_OK;
+  if (!d_codes || !d_lens || !d_out) return fail(KMG_EINVAL, "NULL buffer");
+  KMG_HIP(hipSetDevice(c->device));
+  return gkm_scorer_score_device(c, s, d_codes, d_lens, nq, ldc, (int)ldc, d_wts, ldw, bias, d_out);
+}
+
+int kmg_gkm_scorer_score(kmg_ctx *c, const kmg_scorer *s, const uint8_t *codes, const int32_t *lens,
+                         int64_t nq, int64_t ldc, const uint8_t *wts, int64_t ldw, double bias,
+                         double *out) {
+  if (!c || !s) return fail(KMG_EINVAL, "ctx / scorer is NULL");
+  std::lock_guard<std::mutex> lk(c->mu);
+  int maxlen = 0;
+  int64_t words = 0;
+  KMG_TRY(gkm_scorer_rows(codes, lens, nq, ldc, s->k, &maxlen, &words));
+  KMG_TRY(gkm_scorer_score_check(s, nq, maxlen, wts, ldw));
+  if (nq == 0) return KMG_OK;
+  if (!out) return fail(KMG_EINVAL, "NULL buffer");
+  KMG_HIP(hipSetDevice(c->device));
+  KMG_TRY(c->h_codes.ensure((size_t)nq * ldc));
+  KMG_TRY(c->h_lens.ensure(sizeof(int32_t) * (size_t)nq));
+  KMG_TRY(c->h_out.ensure(sizeof(double) * (size_t)nq));
+  KMG_HIP(hipMemcpyAsync(c->h_codes.p, codes, (size_t)nq * ldc, hipMemcpyHostToDevice, c->stream));
+  KMG_HIP(hipMemcpyAsync(c->h_lens.p, lens, sizeof(int32_t) * nq, hipMemcpyHostToDevice, c->stream));
+  const uint8_t *d_w = nullptr;
+  if (wts) {
+    KMG_TRY(c->gx_wts_in.ensure(std::max<size_t>((size_t)nq * ldw, 16)));
+    if (nq * ldw > 0)
+      KMG_HIP(hipMemcpyAsync(c->gx_wts_in.p, wts, (size_t)nq * ldw, hipMemcpyHostToDevice, c->stream));
+    d_w = c->gx_wts_in.as<uint8_t>();
+  }
+  KMG_TRY(gkm_scorer_score_device(c, s, c->h_codes.as<uint8_t>(), c->h_lens.as<int32_t>(), nq, ldc,
+                                  maxlen, d_w, ldw, bias, c->h_out.as<double>()));
+  KMG_HIP(hipMemcpyAsync(out, c->h_out.p, sizeof(double) * nq, hipMemcpyDeviceToHost, c->stream));
+  KMG_HIP(hipStreamSynchronize(c->stream));
+  return KMG_OK;
+}
+
+int kmg_gkm_scorer_table(kmg_ctx *c, const kmg_scorer *s, double *out) {
+  if (!c || !s || !out) return fail(KMG_EINVAL, "ctx / scorer / out is NULL");
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (s->kind != KMG_GKM)
+    return fail(KMG_EINVAL, "gkm scorer: the scorer was made by kmg_scorer_create");
+  KMG_HIP(hipSetDevice(c->device));
+  KMG_HIP(hipMemcpyAsync(out, s->U.p, sizeof(double) * (size_t)pow4(s->k), hipMemcpyDeviceToHost,
+                         c->stream));
   KMG_HIP(hipStreamSynchronize(c->stream));
   return KMG_OK;
 }

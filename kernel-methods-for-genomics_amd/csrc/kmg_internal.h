@@ -376,6 +376,27 @@ hipError_t launch_score_butterfly(double *T, int k, int nt, int lo, int tg, int 
 hipError_t launch_score(const Packed &pk, int64_t nq, int k, int P, const double *U,
                         const double *dsq, double bias, double *out, hipStream_t s);
 
+// the gkm table scorer (kmg_gkm_scorer_*): 80 fraction bits below the binade of max |beta|,
+// fewer than 2^36 training words (2 strands * 255 * 2^36 * 2^80 < 2^127)
+#define KMG_GKS_FRAC 80
+#define KMG_GKS_MAX_WORDS ((int64_t)1 << 36)
+// tab[2 v], tab[2 v + 1] (low, high limb; cleared first) += fix[2 t], fix[2 t + 1] * wts[t][b]
+// for every valid word b < P of every row t equal to v, with integer atomics (exact in any
+// order); wts uint8 [n][ldw] or nullptr (ones); mw = packed_mw of the records' ldc
+hipError_t launch_gkm_vtab(const Packed &pk, int mw, int64_t n, int l, int P, const uint8_t *wts,
+                           int64_t ldw, const uint64_t *fix, uint64_t *tab, hipStream_t s);
+// T0[v] = tab entry v (rc: + entry rc(v), as integers) rounded to double once, times 2^scale_exp
+hipError_t launch_gkm_vconv(const uint64_t *tab, int l, bool rc, int scale_exp, double *T0,
+                            hipStream_t s);
+// both strands: U[z] = U[min(z, rc(z))], so U[z] and U[rc(z)] hold the same bits
+hipError_t launch_gkm_usym(double *U, int l, hipStream_t s);
+// lanes a query (8, 16, 64, or 256: a workgroup) for rows of at most P words
+int gkm_score_lanes(int P);
+// out[q] = sum_{a < P} wts[q][a] U[word a of record q] (/ dsq[q] when dsq != nullptr) + bias
+hipError_t launch_gkm_score(const Packed &pk, int mw, int64_t nq, int l, int P, int G,
+                            const uint8_t *wts, int64_t ldw, const double *U, const double *dsq,
+                            double bias, double *out, hipStream_t s);
+
 struct SeqSpec {
   const uint8_t *codes;
   const int32_t *lens;

@@ -16,6 +16,10 @@
 // integer (90 fraction bits below the binade of max |beta|, made on the host) and the list
 // sums are integer sums, exact in any order; V[u] is that integer rounded to double once.
 // (2) and (3) add doubles in an order fixed by the launch geometry alone.  No atomics.
+//
+// Section (4) at the end is the gapped k-mer model's table scorer (kmg_gkm_scorer_*): its own
+// weight-table kernel, split by words, with 128-bit integer atomics, and its own scoring
+// kernels, several queries a wave; the butterfly (2) is shared.
 #include "kmg_internal.h"
 
 namespace kmg {
@@ -273,6 +277,298 @@ hipError_t launch_score(const Packed &pk, int64_t nq, int k, int P, const double
   const size_t lds = (size_t)4 * pk.ldp * sizeof(uint32_t);
   hipLaunchKernelGGL(score_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), lds, s, pk, nq, k, P,
                      U, dsq, bias, out);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ (4) gkm table scorer
+// The gapped k-mer model (kmg_gkm_scorer_*) as the same kind of table:
+//   V[v] = sum_t beta_t sum_b w_t[b] [x_t word b = v]     (vtab; both strands: V[v] + V[rc(v)])
+//   U    = sum_{m <= d} c[m] E_m V                        (the butterfly above, nt = d + 1)
+//   f(q) = sum_a u_q[a] U[q_a] (/ sqrt(K_qq)) + bias      (score)
+// The work of (vtab) is split by words: a workgroup stages a batch of records, one lane takes
+// one word and adds beta_t w_t[b], a 128-bit integer, into the word's table entry with two
+// 64-bit integer atomics.  Integer sums are exact in any order, so the table does not depend
+// on the grid, the batch or the order the atomics land in.  Fixed point: KMG_GKS_FRAC = 80
+// fraction bits below 2^E > max |beta|, so |beta_t| 2^(80 - E) < 2^80 and
+//   2 strands * 255 * (fewer than 2^36 words, KMG_GKS_MAX_WORDS) * 2^80 < 2^125 < 2^127;
+// a beta is cut to that grid once on the host (less than 2^(E - 80) off).
+// Rows of any length: a record is staged in segments of GKS_SEG word starts, in the record's
+// own layout (code words, then mask words), so pk_window reads a segment as it reads a record.
+constexpr int GKS_SEG = 2048;
+constexpr int GKS_CW = GKS_SEG / 16 + 2;
+constexpr int GKS_MW = GKS_SEG / 32 + 2;
+
+// word i of the staged form of segment seg: code words [0, cws), mask words [cws, cws + mws);
+// past the record: no letters, every one of them masked
+__device__ __forceinline__ uint32_t gks_word(const uint32_t *rec, int cw, int mw, int cws, int seg,
+                                             int i) {
+  if (i < cws) {
+    const int s = seg * (GKS_SEG / 16) + i;
+    return s < cw ? rec[s] : 0u;
+  }
+  const int s = seg * (GKS_SEG / 32) + (i - cws);
+  return s < mw ? rec[cw + s] : 0xFFFFFFFFu;
+}
+
+// *p (low limb, high limb) += (lo, hi) mod 2^128: the carry out of the low limb is read off
+// the value the first atomic returns, so every interleaving of such adds gives the exact sum
+template <typename T>
+__device__ __forceinline__ void gks_atomic_add(T *p, uint64_t lo, uint64_t hi) {
+  const uint64_t old = atomicAdd(p, (unsigned long long)lo);
+  hi += (old + lo < lo) ? 1 : 0;
+  if (hi != 0) atomicAdd(p + 1, (unsigned long long)hi);
+}
+
+// PRIV (l <= 6): the whole table, 16 bytes a key, private to the workgroup in LDS (ds 64-bit
+// atomics), flushed once with global atomics; else global atomics a word.  A batch is B
+// (row, segment) items of ps = min(P, GKS_SEG) word starts each.
+template <bool PRIV>
+__global__ __launch_bounds__(256) void gkm_vtab_kernel(Packed pk, int mw, int64_t n, int l, int P,
+                                                       int B, const uint8_t *__restrict__ wts,
+                                                       int64_t ldw,
+                                                       const uint64_t *__restrict__ fix,
+                                                       unsigned long long *__restrict__ tab) {
+  extern __shared__ __align__(16) unsigned long long gks_priv[];  // [2 * 4^l] (PRIV), then records
+  const int nkeys = 1 << (2 * l);
+  uint32_t *srec = (uint32_t *)(gks_priv + (PRIV ? 2 * nkeys : 0));
+  const int cws = min(pk.cw, GKS_CW), mws = min(mw, GKS_MW), rs = cws + mws;
+  const int nseg = (P + GKS_SEG - 1) / GKS_SEG, ps = min(P, GKS_SEG);
+  const int64_t nitems = n * nseg;
+  if (PRIV) {
+    for (int t = threadIdx.x; t < 2 * nkeys; t += 256) gks_priv[t] = 0;
+  }
+  for (int64_t it0 = (int64_t)blockIdx.x * B; it0 < nitems; it0 += (int64_t)gridDim.x * B) {
+    const int nb = (int)min((int64_t)B, nitems - it0);
+    __syncthreads();  // the table is cleared / the last batch is done with srec
+    for (int t = threadIdx.x; t < nb * rs; t += 256) {
+      const int b = t / rs;
+      const int64_t row = (it0 + b) / nseg;
+      srec[t] = gks_word(pk.w + row * pk.ldp, pk.cw, mw, cws, (int)((it0 + b) % nseg), t - b * rs);
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < nb * ps; t += 256) {
+      const int b = t / ps, a = t - b * ps;
+      const int64_t row = (it0 + b) / nseg;
+      const int ga = (int)((it0 + b) % nseg) * GKS_SEG + a;  // the word's start in its row
+      if (ga >= P) continue;
+      const uint32_t code = pk_window(srec + b * rs, cws, a, l);
+      if (code == KMG_INVALID) continue;
+      const uint64_t wv = wts ? wts[row * ldw + ga] : 1;
+      // beta_t * w (two's complement, mod 2^128)
+      const uint64_t lo = fix[2 * row], hi = fix[2 * row + 1];
+      const uint64_t plo = lo * wv, phi = hi * wv + __umul64hi(lo, wv);
+      if ((plo | phi) == 0) continue;
+      if (PRIV)
+        gks_atomic_add(gks_priv + 2 * (size_t)code, plo, phi);
+      else
+        gks_atomic_add(tab + 2 * (size_t)code, plo, phi);
+    }
+  }
+  if (PRIV) {
+    __syncthreads();
+    for (int key = threadIdx.x; key < nkeys; key += 256) {
+      const uint64_t lo = gks_priv[2 * key], hi = gks_priv[2 * key + 1];
+      if ((lo | hi) != 0) gks_atomic_add(tab + 2 * (size_t)key, lo, hi);
+    }
+  }
+}
+
+// reverse complement of a word of l letters (A<->T, C<->G: 3 - letter; letters reversed)
+__device__ __forceinline__ uint32_t gks_rc(uint32_t v, int l) {
+  uint32_t x = ~v;
+  x = ((x >> 2) & 0x33333333u) | ((x & 0x33333333u) << 2);
+  x = ((x >> 4) & 0x0F0F0F0Fu) | ((x & 0x0F0F0F0Fu) << 4);
+  x = __builtin_bswap32(x);
+  return x >> (32 - 2 * l);
+}
+
+// T_0[v] = the table entry rounded to double once; rc: the integer sum of the entries of v
+// and rc(v) rounded once (a palindrome counts on both strands, so its own entry twice)
+__global__ __launch_bounds__(256) void gkm_vconv_kernel(const unsigned long long *__restrict__ tab,
+                                                        int l, int rc, int scale_exp,
+                                                        double *__restrict__ T0) {
+  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (v >= ((int64_t)1 << (2 * l))) return;
+  Fix128 a{tab[2 * v], (int64_t)tab[2 * v + 1]};
+  if (rc) {
+    const uint32_t r = gks_rc((uint32_t)v, l);
+    fix_add(a, tab[2 * (size_t)r], (int64_t)tab[2 * (size_t)r + 1]);
+  }
+  T0[v] = fix_to_double(a, scale_exp);
+}
+
+__global__ __launch_bounds__(256) void gkm_tab_clear_kernel(unsigned long long *__restrict__ tab,
+                                                            int64_t nwords) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t < nwords) tab[t] = 0;
+}
+
+// both strands: the butterfly adds the letters of a digit in letter order, which the reverse
+// complement permutes, so U[z] and U[rc(z)] can differ in the last bits; the entry of the
+// smaller of z, rc(z) is taken for both (entries with z <= rc(z) are only read)
+__global__ __launch_bounds__(256) void gkm_usym_kernel(double *__restrict__ U, int l) {
+  const int64_t z = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (z >= ((int64_t)1 << (2 * l))) return;
+  const uint32_t r = gks_rc((uint32_t)z, l);
+  if ((int64_t)r < z) U[z] = U[r];
+}
+
+int gkm_vtab_batch(int P) {
+  // 1024 word starts a batch (four a lane) where the rows are short, 32 rows at the most
+  const int ps = P < GKS_SEG ? P : GKS_SEG;
+  int B = (1024 + ps - 1) / ps;
+  return B < 1 ? 1 : B > 32 ? 32 : B;
+}
+
+hipError_t launch_gkm_vtab(const Packed &pk, int mw, int64_t n, int l, int P, const uint8_t *wts,
+                           int64_t ldw, const uint64_t *fix, uint64_t *tab, hipStream_t s) {
+  const int64_t nkeys = (int64_t)1 << (2 * l);
+  hipLaunchKernelGGL(gkm_tab_clear_kernel, dim3((unsigned)((2 * nkeys + 255) / 256)), dim3(256), 0, s,
+                     (unsigned long long *)tab, 2 * nkeys);
+  if (n == 0 || P <= 0) return hipGetLastError();  // no word anywhere: the table stays zero
+  const int B = gkm_vtab_batch(P);
+  const int cws = pk.cw < GKS_CW ? pk.cw : GKS_CW, mws = mw < GKS_MW ? mw : GKS_MW;
+  const int nseg = (P + GKS_SEG - 1) / GKS_SEG;
+  const int64_t nbatch = (n * nseg + B - 1) / B;
+  const size_t rec_lds = (size_t)B * (cws + mws) * sizeof(uint32_t);
+  if (l <= 6) {
+    // a workgroup flushes 4^l entries: give it at least four words a key before it does
+    const int64_t words = n * (int64_t)P;
+    int64_t grid = words / (4 * nkeys);
+    grid = grid < 1 ? 1 : grid > 256 ? 256 : grid;
+    if (grid > nbatch) grid = nbatch;
+    hipLaunchKernelGGL((gkm_vtab_kernel<true>), dim3((unsigned)grid), dim3(256),
+                       (size_t)nkeys * 16 + rec_lds, s, pk, mw, n, l, P, B, wts, ldw, fix,
+                       (unsigned long long *)tab);
+  } else {
+    const int64_t grid = nbatch < 65536 ? nbatch : 65536;
+    hipLaunchKernelGGL((gkm_vtab_kernel<false>), dim3((unsigned)grid), dim3(256), rec_lds, s, pk, mw,
+                       n, l, P, B, wts, ldw, fix, (unsigned long long *)tab);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_gkm_vconv(const uint64_t *tab, int l, bool rc, int scale_exp, double *T0,
+                            hipStream_t s) {
+  const int64_t nkeys = (int64_t)1 << (2 * l);
+  hipLaunchKernelGGL(gkm_vconv_kernel, dim3((unsigned)((nkeys + 255) / 256)), dim3(256), 0, s,
+                     (const unsigned long long *)tab, l, rc ? 1 : 0, scale_exp, T0);
+  return hipGetLastError();
+}
+
+hipError_t launch_gkm_usym(double *U, int l, hipStream_t s) {
+  const int64_t nkeys = (int64_t)1 << (2 * l);
+  hipLaunchKernelGGL(gkm_usym_kernel, dim3((unsigned)((nkeys + 255) / 256)), dim3(256), 0, s, U, l);
+  return hipGetLastError();
+}
+
+// G lanes a query, 256 / G queries a workgroup (G = 8, 16, 64): the records, and the weights
+// where given, staged in LDS; lane j of a query takes its words a = j, j + G, ... in
+// ascending order, each product u[a] * U[code] rounded before it is added; a fixed xor tree of
+// width G (every lane of the group ends with the same bits); / sqrt(K_qq), + bias; the
+// workgroup's results leave in one store.  P <= 1024 words (the host picks G from P).
+template <int G>
+__global__ __launch_bounds__(256) void gkm_score_kernel(Packed pk, int64_t nq, int l, int P,
+                                                        const uint8_t *__restrict__ wts,
+                                                        int64_t ldw, const double *__restrict__ U,
+                                                        const double *__restrict__ dsq, double bias,
+                                                        double *__restrict__ out) {
+  constexpr int QW = 256 / G;
+  extern __shared__ __align__(16) uint32_t gks_q[];  // [QW][ldp] records, then [QW][pw] weight bytes
+  __shared__ double res[QW];
+  const int pw = (P + 3) & ~3;
+  uint8_t *swt = (uint8_t *)(gks_q + QW * pk.ldp);
+  const int64_t q0 = (int64_t)blockIdx.x * QW;
+  const int nqw = (int)min((int64_t)QW, nq - q0);
+  for (int t = threadIdx.x; t < nqw * (int)pk.ldp; t += 256) gks_q[t] = pk.w[q0 * pk.ldp + t];
+  if (wts)
+    for (int t = threadIdx.x; t < nqw * P; t += 256) {
+      const int qi = t / P, a = t - qi * P;
+      swt[qi * pw + a] = wts[(q0 + qi) * ldw + a];
+    }
+  __syncthreads();
+  const int qi = threadIdx.x / G, sub = threadIdx.x % G;
+  double s = 0.0;
+  if (qi < nqw) {
+    const uint32_t *srec = gks_q + qi * pk.ldp;
+    for (int a = sub; a < P; a += G) {
+      const uint32_t code = pk_window(srec, pk.cw, a, l);
+      if (code == KMG_INVALID) continue;
+      if (wts)
+        s += (double)swt[qi * pw + a] * U[code];
+      else
+        s += U[code];
+    }
+  }
+#pragma unroll
+  for (int d = G / 2; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+  if (sub == 0 && qi < nqw) res[qi] = dsq ? s / dsq[q0 + qi] + bias : s + bias;
+  __syncthreads();
+  if (threadIdx.x < nqw) out[q0 + threadIdx.x] = res[threadIdx.x];
+}
+
+// the workgroup-wide form, rows of any length: one query a workgroup, the record staged a
+// segment at a time; lane t takes the words a = t, t + 256, ... of every segment in ascending
+// order, then the xor tree of each wave and the four wave sums added in wave order
+__global__ __launch_bounds__(256) void gkm_score_wide_kernel(Packed pk, int mw, int64_t nq, int l,
+                                                             int P, const uint8_t *__restrict__ wts,
+                                                             int64_t ldw,
+                                                             const double *__restrict__ U,
+                                                             const double *__restrict__ dsq,
+                                                             double bias, double *__restrict__ out) {
+  __shared__ uint32_t srec[GKS_CW + GKS_MW];
+  __shared__ uint8_t swt[GKS_SEG];
+  __shared__ double part[4];
+  const int64_t q = blockIdx.x;
+  const uint32_t *rec = pk.w + q * pk.ldp;
+  const int nseg = (P + GKS_SEG - 1) / GKS_SEG;
+  double s = 0.0;
+  for (int seg = 0; seg < nseg; ++seg) {
+    const int a0 = seg * GKS_SEG, na = min(GKS_SEG, P - a0);
+    __syncthreads();
+    for (int t = threadIdx.x; t < GKS_CW + GKS_MW; t += 256)
+      srec[t] = gks_word(rec, pk.cw, mw, GKS_CW, seg, t);
+    if (wts)
+      for (int t = threadIdx.x; t < na; t += 256) swt[t] = wts[q * ldw + a0 + t];
+    __syncthreads();
+    for (int a = threadIdx.x; a < na; a += 256) {
+      const uint32_t code = pk_window(srec, GKS_CW, a, l);
+      if (code == KMG_INVALID) continue;
+      if (wts)
+        s += (double)swt[a] * U[code];
+      else
+        s += U[code];
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double t = ((part[0] + part[1]) + part[2]) + part[3];
+    out[q] = dsq ? t / dsq[q] + bias : t + bias;
+  }
+}
+
+// lanes a query from the word bound P alone (ldc in both the host and the device form):
+// at most 4 words a lane on 8 lanes, 8 on 16, 16 on a wave, then a workgroup
+int gkm_score_lanes(int P) { return P <= 32 ? 8 : P <= 128 ? 16 : P <= 1024 ? 64 : 256; }
+
+hipError_t launch_gkm_score(const Packed &pk, int mw, int64_t nq, int l, int P, int G,
+                            const uint8_t *wts, int64_t ldw, const double *U, const double *dsq,
+                            double bias, double *out, hipStream_t s) {
+  if (nq == 0) return hipSuccess;
+  if (G != 256 && P > 1024) return hipErrorInvalidValue;  // (the staged record is the whole row)
+  const int qw = G == 256 ? 1 : 256 / G;
+  const dim3 grid((unsigned)((nq + qw - 1) / qw));
+  const size_t lds = (size_t)qw * (pk.ldp * sizeof(uint32_t) + (wts ? (size_t)((P + 3) & ~3) : 0));
+  switch (G) {
+    case 8: hipLaunchKernelGGL((gkm_score_kernel<8>), grid, dim3(256), lds, s, pk, nq, l, P, wts, ldw, U, dsq, bias, out); break;
+    case 16: hipLaunchKernelGGL((gkm_score_kernel<16>), grid, dim3(256), lds, s, pk, nq, l, P, wts, ldw, U, dsq, bias, out); break;
+    case 64: hipLaunchKernelGGL((gkm_score_kernel<64>), grid, dim3(256), lds, s, pk, nq, l, P, wts, ldw, U, dsq, bias, out); break;
+    case 256: hipLaunchKernelGGL(gkm_score_wide_kernel, grid, dim3(256), 0, s, pk, mw, nq, l, P, wts, ldw, U, dsq, bias, out); break;
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 

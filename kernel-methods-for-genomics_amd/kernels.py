@@ -22,7 +22,7 @@ from kmgram.params import gkm_center_weights
 
 __all__ = [
     "get_spectrum_K", "get_WD_K", "get_WDShifts_K", "get_mismatch_K", "get_LA_K",
-    "get_string_K", "get_gappy_K", "get_gkm_K", "get_gkm_cross_K", "center_K", "normalize_K",
+    "get_string_K", "get_gappy_K", "get_gkm_K", "get_gkm_cross_K", "get_gkm_scorer", "center_K", "normalize_K",
     "select_method",
     "beta", "delta", "letter_to_num", "format", "S", "get_WD_d", "get_WDShifts_d", "K_k",
     "affine_align", "Smith_Waterman", "get_phi_u", "get_phi_km", "gappy_k", "B_k", "rec",
@@ -97,6 +97,19 @@ def get_gkm_cross_K(Xa, Xb, l, k=None, d=None, *, both_strands=False, center_wei
         wa, wb = ([gkm_center_weights(len(s), l, M, H) for s in side] for side in (sa, sb))
     return _eng().gkm_cross(sa, sb, l, k, d, both_strands=both_strands, weights_a=wa,
                             weights_b=wb, filter=filter)
+
+
+def get_gkm_scorer(X, coef, l, k=None, d=None, *, both_strands=False, center_weights=None,
+                   filter=None):
+    """The model sum_t coef[t] K(., X row t) of ``get_gkm_cross_K``'s kernel (normalised, same
+    arguments) as a table scorer: ``score(Xq, bias)`` is ``get_gkm_cross_K(Xq, X, ...) @ coef +
+    bias`` without the block, ``lmer_weights()`` the 4^l l-mer weights (gkm-SVM's gkmpredict
+    and weight export; ``GramEngine.gkm_scorer``).  center_weights=(M, H) weighs the rows of X
+    and every scored row as ``get_gkm_cross_K`` does; not together with filter (the
+    normalised kernel has no weighted filter; ``GramEngine.gkm_scorer(normalize=False)`` serves
+    the two together)."""
+    return _eng().gkm_scorer(_seqs(X), coef, l, k, d, both_strands=both_strands, filter=filter,
+                             center_weights=center_weights)
 
 
 # ----------------------------------------------------------------------- helpers

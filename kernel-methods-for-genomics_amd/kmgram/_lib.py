@@ -41,6 +41,8 @@ EXPORTS = (
     "kmg_scorer_create", "kmg_scorer_score", "kmg_scorer_score_device", "kmg_scorer_destroy",
     "kmg_gkm_cross", "kmg_gkm_cross_device", "kmg_gkm_cross_w", "kmg_gkm_cross_w_device",
     "kmg_gkm_profile", "kmg_gkm_profile_device", "kmg_gkm_cross_f", "kmg_gkm_cross_f_device",
+    "kmg_gkm_scorer_create", "kmg_gkm_scorer_score", "kmg_gkm_scorer_score_device",
+    "kmg_gkm_scorer_table",
 )
 KMG_FEATURES_BCAST = 1
 KMG_FACTOR_CHOLESKY, KMG_FACTOR_LU_ASYMMETRIC, KMG_FACTOR_LU_INDEFINITE = 1, 2, 3
@@ -125,6 +127,11 @@ def load():
             "kmg_scorer_score": ([P, P, P, P, I64, I64, D, P], ctypes.c_int),
             "kmg_scorer_score_device": ([P, P, P, P, I64, I64, D, P], ctypes.c_int),
             "kmg_scorer_destroy": ([P, P], ctypes.c_int),
+            "kmg_gkm_scorer_create": ([P, ctypes.POINTER(KmgParams), P, P, I64, I64, P, I64, P, P,
+                                       I32, ctypes.POINTER(P)], ctypes.c_int),
+            "kmg_gkm_scorer_score": ([P, P, P, P, I64, I64, P, I64, D, P], ctypes.c_int),
+            "kmg_gkm_scorer_score_device": ([P, P, P, P, I64, I64, P, I64, D, P], ctypes.c_int),
+            "kmg_gkm_scorer_table": ([P, P, P], ctypes.c_int),
             "kmg_normalize": ([P, P, I64, I64, ctypes.POINTER(I32)], ctypes.c_int),
             "kmg_center": ([P, P, I64, P, I64, I64], ctypes.c_int),
             "kmg_dmalloc": ([P, ctypes.POINTER(P), SZ], ctypes.c_int),
@@ -230,6 +237,37 @@ class Scorer:
             self.close()
         except Exception:
             pass
+
+
+class GkmScorer(Scorer):
+    """A fitted gapped k-mer model as one l-mer table on the device (kmg_gkm_scorer_*)."""
+
+    def __init__(self, ctx, handle, l):
+        super().__init__(ctx, handle)
+        self.l = l
+
+    def score(self, codes, lens, bias=0.0, weights=None):
+        """float64 [nq]: f(q) for every row of codes; weights uint8 [nq, ldw] or None (ones)."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        nq, ldc = codes.shape
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint8).reshape(nq, -1)
+        out = np.empty(nq, dtype=np.float64)
+        check(self.ctx.lib.kmg_gkm_scorer_score(
+            self.ctx.handle, self._h, ptr(codes), ptr(lens), nq, ldc, ptr(w),
+            0 if w is None else w.shape[1], float(bias), ptr(out)))
+        return out
+
+    def score_device(self, d_codes, d_lens, nq, ldc, bias, d_out, d_wts=None, ldw=0):
+        """The same on device pointers, on the context stream, without synchronising."""
+        check(self.ctx.lib.kmg_gkm_scorer_score_device(self.ctx.handle, self._h, d_codes, d_lens,
+                                                       nq, ldc, d_wts, ldw, float(bias), d_out))
+
+    def table(self):
+        """float64 [4^l]: the l-mer weights U (kmg_gkm_scorer_table)."""
+        out = np.empty(4 ** self.l, dtype=np.float64)
+        check(self.ctx.lib.kmg_gkm_scorer_table(self.ctx.handle, self._h, ptr(out)))
+        return out
 
 
 class Context:
@@ -379,6 +417,25 @@ class Context:
         check(self.lib.kmg_scorer_create(self._h, ctypes.byref(params), ptr(codes), ptr(lens), n,
                                          ldc, ptr(coef), ctypes.byref(h)))
         return Scorer(self, h)
+
+    def gkm_scorer(self, params, codes, lens, coef, weights=None, filter=None):
+        """Scorer of the gkm model sum_t coef[t] K(., row t) (kmg_gkm_scorer_create; params from
+        ``params.gkm`` / ``params.gkm_profile``): weights uint8 [n, ldw] position weights of the
+        rows' words or None, filter float64 [params.m + 1] or None (C(l - m, k) from params)."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        coef = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1)
+        n, ldc = codes.shape
+        if coef.shape[0] != n:
+            raise ValueError(f"coef has {coef.shape[0]} entries for {n} rows")
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint8).reshape(n, -1)
+        f = None if filter is None else np.ascontiguousarray(filter, dtype=np.float64).reshape(-1)
+        h = ctypes.c_void_p()
+        check(self.lib.kmg_gkm_scorer_create(
+            self._h, ctypes.byref(params), ptr(codes), ptr(lens), n, ldc, ptr(w),
+            0 if w is None else w.shape[1], ptr(coef), ptr(f), 0 if f is None else len(f),
+            ctypes.byref(h)))
+        return GkmScorer(self, h, params.k)
 
     def gram_device(self, params, d_codes, d_lens, n, ldc, row0, row1, out_dtype, d_out, ld):
         check(self.lib.kmg_gram_device(self._h, ctypes.byref(params), d_codes, d_lens, n, ldc,

@@ -331,6 +331,48 @@ class GramEngine:
         codes, lens = E.encode(seqs)
         return EngineScorer(self, self.ctx.scorer(p, codes, lens, coef), mm)
 
+    def gkm_scorer(self, seqs, coef, l, k=None, d=None, *, both_strands=False, weights=None,
+                   filter=None, normalize=True, center_weights=None):
+        """Scorer of f(q) = sum_t coef[t] K(q, seqs[t]) + bias for the gapped k-mer kernel K of
+        ``gkm_cross`` with the same (l, k, d, both_strands, filter, normalize), from one table
+        of 4^l l-mer weights and without any Gram block (kmg_gkm_scorer_create: gkm-SVM's
+        gkmpredict and l-mer weight export).  l <= 12 and d <= 4 (a filter of at most five
+        coefficients), else KmgUnsupported.  weights: the training rows' position weights as in
+        ``gkm_cross(weights_b=)``; unlike the block, a filter and weights are served together
+        when normalize=False.  center_weights=(M, H): ``params.gkm_center_weights`` of every
+        training row, and of every scored row that brings no weights of its own.  Under
+        normalize=True a training row without a valid word whose coef is not 0 raises
+        ValueError; a scored row without one gives NaN.  Returns an ``EngineGkmScorer``."""
+        seqs, l = list(seqs), int(l)
+        if filter is not None:
+            filter = np.asarray(filter, dtype=np.float64)
+            if filter.ndim != 1 or not 1 <= filter.shape[0] <= l:
+                raise ValueError(f"gkm: filter needs 1..l coefficients c[0..d], d <= l-1 (l={l})")
+            if d is not None and int(d) != filter.shape[0] - 1:
+                raise ValueError(f"gkm: d={d} but the filter has {filter.shape[0]} coefficients")
+            d = filter.shape[0] - 1
+            p = (P.gkm_profile(l, d, both_strands, normalize) if k is None
+                 else P.gkm(l, k, d, normalize, both_strands))
+        elif k is None:
+            raise ValueError("gkm: k is needed where no filter= is given")
+        else:
+            p = P.gkm(l, k, d, normalize, both_strands)
+        coef = np.asarray(coef, dtype=np.float64).reshape(-1)
+        if coef.shape[0] != len(seqs):
+            raise ValueError(f"gkm: coef has {coef.shape[0]} entries for {len(seqs)} sequences")
+        if center_weights is not None and weights is None:
+            weights = [P.gkm_center_weights(len(s), l, *center_weights) for s in seqs]
+        w = self._gkm_weights("t", weights, seqs, l, False)
+        if normalize:
+            word = re.compile("[ACGT]{%d}" % l)
+            for i, s in enumerate(seqs):
+                if coef[i] != 0 and not word.search(s):
+                    raise ValueError(f"gkm: training sequence {i} has no all-ACGT word of length "
+                                     f"{l}; its diagonal would be 0 under normalize=True")
+        codes, lens = E.encode(seqs)
+        return EngineGkmScorer(self, self.ctx.gkm_scorer(p, codes, lens, coef, w, filter), l,
+                               center_weights)
+
     def _check_scored(self, seqs, mm):
         """Mismatch rows: get_mismatch_K's own refusals (see ``mismatch``)."""
         if not mm:
@@ -389,6 +431,35 @@ class EngineScorer:
         self.engine._check_scored(seqs, self._mm)
         codes, lens = E.encode(seqs)
         return self._s.score(codes, lens, bias)
+
+    def close(self):
+        self._s.close()
+
+
+class EngineGkmScorer:
+    """What ``GramEngine.gkm_scorer`` returns: ``score(seqs, bias, weights)`` on strings and
+    ``lmer_weights()``, the 4^l l-mer weights of the model."""
+
+    def __init__(self, engine, scorer, l, center_weights=None):
+        self.engine, self._s, self.l, self._center = engine, scorer, l, center_weights
+
+    def score(self, seqs, bias=0.0, weights=None):
+        """float64 [len(seqs)]: f(q) + bias for strings (or a DataFrame's ``seq`` column);
+        weights as in ``gkm_cross(weights_a=)``."""
+        seqs = E.as_sequence_list(seqs)
+        if not seqs:
+            return np.zeros(0, dtype=np.float64)
+        if weights is None and self._center is not None:
+            weights = [P.gkm_center_weights(len(s), self.l, *self._center) for s in seqs]
+        w = GramEngine._gkm_weights("q", weights, seqs, self.l, False)
+        codes, lens = E.encode(seqs)
+        return self._s.score(codes, lens, bias, w)
+
+    def lmer_weights(self):
+        """float64 [4^l]: the score of every l-mer under the model (deltaSVM's input), word z
+        at its base-4 code, A C G T = 0 1 2 3, first letter most significant; with
+        both_strands the entries of a word and of its reverse complement hold the same bits."""
+        return self._s.table()
 
     def close(self):
         self._s.close()

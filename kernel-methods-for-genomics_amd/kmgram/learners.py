@@ -89,6 +89,19 @@ class _GramLearner:
         sv = default_engine().scorer(method, [seqs[i] for i in self.idx_sv], self.a)
         return _ModelScorer(sv, float(self.b))
 
+    def gkm_scorer(self, seqs, l, k=None, d=None, **kw):
+        """``scorer`` for a model fitted on a gapped k-mer Gram, which has no method string:
+        (l, k, d) and the keywords (both_strands, weights, center_weights, filter, normalize)
+        are those K was built with and go to ``GramEngine.gkm_scorer``; ``weights`` holds a row
+        for every sequence of ``seqs``."""
+        seqs = list(seqs)
+        if len(seqs) != len(self.ID):
+            raise ValueError(f"{len(seqs)} sequences for the {len(self.ID)} rows of K")
+        if kw.get("weights") is not None:
+            kw["weights"] = [kw["weights"][i] for i in self.idx_sv]
+        sv = default_engine().gkm_scorer([seqs[i] for i in self.idx_sv], self.a, l, k, d, **kw)
+        return _ModelScorer(sv, float(self.b))
+
     def score(self, pred, y):
         """Accuracy of -1/1 predictions (KRR.py:58-66)."""
         label = y if isinstance(y, np.ndarray) else np.array(y.loc[:, "Bound"])
