@@ -380,6 +380,39 @@ int kmg_gkm_scorer_score_device(kmg_ctx *ctx, const kmg_scorer *s, const uint8_t
  * indexed as the library codes words (base 4, A C G T = 0 1 2 3, first letter most
  * significant).  Under strands = 2, out[z] and out[rc(z)] hold the same bits.  Synchronous. */
 int kmg_gkm_scorer_table(kmg_ctx *ctx, const kmg_scorer *s, double *out);
+/* Substitution map (in-silico saturation mutagenesis; deltaSVM for every variant of a query):
+ * out is double [nq][ld_out][4], out[q][i][b] = f_raw(q with letter b at position i) - f_raw(q),
+ * b = A C G T = 0..3, as deltaSVM defines it: a sum of l-mer weight differences over the at
+ * most l words that cover i.  With U the table above, P = n - l + 1 the words of a row of n
+ * letters and u its position weights (wts as in kmg_gkm_scorer_score; NULL: ones):
+ *   S_b(i) = sum, over max(0, i - l + 1) <= a <= min(i, P - 1) in ascending a from +0.0, of
+ *            u[a] * U[word a with its letter at offset i - a replaced by b], the product
+ *            rounded before it is added, over the words whose other letters are all A/C/G/T
+ *   R(i)   = S_{q_i}(i) where q_i is A/C/G/T, +0.0 where it is not
+ *   out[q][i][b] = S_b(i) - R(i)
+ * so out[q][i][q_i] is +0.0, a position that holds an N gets the four full sums, a word with a
+ * second non-ACGT letter or weight 0 adds nothing, and positions i >= n up to ld_out, like every
+ * position of a row shorter than l, are +0.0: every element is written.  The bias cancels and
+ * beta_t = coef[t] / sqrt(K_tt) of a normalised model is in the table; the query's own
+ * 1 / sqrt(K_qq) is NOT applied (a mutant has its own diagonal), so no diagonal is taken and
+ * weights are accepted with any model.  strands = 2 changes nothing: the table is symmetric.
+ * The order of the adds is fixed by the definition alone: the same bytes for a query alone, in a
+ * batch, in any slab, in the host form and in the device form.
+ *   Host form: ld_out at least the longest row, else KMG_EINVAL; ldw short of the longest
+ *   row's words, or a scorer of kmg_scorer_create, is KMG_EINVAL; nq = 0 is KMG_OK and writes
+ *   nothing; all of it is checked before any allocation or launch.  The queries are packed
+ *   once and mapped in slabs of queries whose device output stays within 256 MB of context
+ *   workspace (one query at the least; KMG_MUTATE_SLAB forces the slab size in queries).
+ * Synchronous.  Stage "mutate" (and "pack"). */
+int kmg_gkm_scorer_mutate(kmg_ctx *ctx, const kmg_scorer *s, const uint8_t *codes,
+                          const int32_t *lens, int64_t nq, int64_t ldc, const uint8_t *wts,
+                          int64_t ldw, double *out, int64_t ld_out);
+/* The same on device pointers (rows up to ldc symbols bound the checks: ld_out at least ldc,
+ * ldw at least ldc - l + 1): runs on the context stream and returns without synchronising.
+ * Same bits as the host form. */
+int kmg_gkm_scorer_mutate_device(kmg_ctx *ctx, const kmg_scorer *s, const uint8_t *d_codes,
+                                 const int32_t *d_lens, int64_t nq, int64_t ldc,
+                                 const uint8_t *d_wts, int64_t ldw, double *d_out, int64_t ld_out);
 
 /*
  * The full K of all n rows into HOST memory h_out (row stride ld_host elements; e.g. a
@@ -555,6 +588,7 @@ int kmg_stream(kmg_ctx *ctx, void **hip_stream);
  * "pack" (2-bit packing of the input), "slots" (mismatch slot / pair tables, neighbourhood
  * lists), "lists" (neighbourhood-list sizes and starts), "combine",
  * "vtab" / "butterfly" / "score" (kmg_scorer_*: weight table, Hamming DP, query scoring),
+ * "mutate" (the substitution-map kernel of kmg_gkm_scorer_mutate*),
  * "gkm" (the tiled gapped k-mer Gram kernel, inside the call's "gram" stage),
  * "gkmx" (the rectangular gkm kernel of kmg_gkm_cross* and kmg_gkm_profile*; its diagonals
  * count under "diag", the filter kernel of kmg_gkm_cross_f* past four bins under "combine"),

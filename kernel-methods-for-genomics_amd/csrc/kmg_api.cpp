@@ -94,12 +94,12 @@ const char *kStageNames[] = {"count",   "scan",     "place", "fine",    "diag",
                              "gram",    "extract",  "pack",  "features", "combine",
                              "solve",   "slots",    "memset", "gather", "unpack",
                              "mirror",  "lists",    "nbfill", "vtab",   "butterfly",
-                             "score",   "gkm",      "gkmx"};
-constexpr int kNumStages = 23;
+                             "score",   "gkm",      "gkmx",  "mutate"};
+constexpr int kNumStages = 24;
 enum {
   ST_COUNT, ST_SCAN, ST_PLACE, ST_FINE, ST_DIAG, ST_GRAM, ST_EXTRACT, ST_PACK, ST_FEATURES,
   ST_COMBINE, ST_SOLVE, ST_SLOTS, ST_MEMSET, ST_GATHER, ST_UNPACK, ST_MIRROR, ST_LISTS,
-  ST_NBFILL, ST_VTAB, ST_BUTTERFLY, ST_SCORE, ST_GKM, ST_GKMX
+  ST_NBFILL, ST_VTAB, ST_BUTTERFLY, ST_SCORE, ST_GKM, ST_GKMX, ST_MUTATE
 };
 
 // Tuning knobs: read from the environment once per context (kmg_create) and again only on
@@ -171,6 +171,8 @@ struct Tuning {
                             // 16-row tile at the least: 0 gives 16-row slabs)
   int gkm_score_g = 0;      // KMG_GKM_SCORE_G: lanes a query of the gkm table scorer, 8 / 16 / 64 /
                             // 256 (0 auto: from the row bound, gkm_score_lanes; timing runs only)
+  int mutate_slab = 0;      // KMG_MUTATE_SLAB: queries a slab of kmg_gkm_scorer_mutate's host form
+                            // (0 auto: what 256 MB of device output hold, one query at the least)
   int check = 0;            // KMG_CHECK: 1 validate the neighbourhood lists' metadata after
                             // every fill (nb_check_kernel; one host sync a build) and fail with
                             // KMG_EINTERNAL before any Gram launch reads past a list; 2 the
@@ -219,6 +221,7 @@ void read_tuning(Tuning &t) {
   t.dense_half = env_or("KMG_DENSE_HALF", d.dense_half);
   t.gkm_prof_ws = std::max(0, std::min(65536, env_or("KMG_GKM_PROF_WS", d.gkm_prof_ws)));
   t.gkm_score_g = env_or("KMG_GKM_SCORE_G", d.gkm_score_g);
+  t.mutate_slab = std::max(0, env_or("KMG_MUTATE_SLAB", d.mutate_slab));
   t.check = env_or("KMG_CHECK", d.check);
   if (getenv("KMG_MM_CHUNK") == nullptr) t.mm_chunk = 0;  // 0: per-formulation default
 }
@@ -256,6 +259,7 @@ struct kmg_ctx {
   DevBuf gx_wts, gx_wts_in;         // kmg_gkm_cross_w: the laid-out weights of A, then B; the
                                     // host path's copies of the caller's arrays
   DevBuf gx_prof;                   // kmg_gkm_cross_f, filters past four bins: a row slab's profile
+  DevBuf mut_out;                   // kmg_gkm_scorer_mutate: a query slab's map (256 MB at most)
   Tuning tune;
   DevBuf cmb_k, cmb_ptrs, cmb_vec, cmb_out, cmb_tmp;  // combination consumers (host path)
   DevBuf sv_mat, sv_vec, sv_info;  // dense learners: factorised system, vectors, info/ipiv
@@ -1671,7 +1675,8 @@ int kmg_destroy(kmg_ctx *c) {
                     &c->tri_stage, &c->tri_scratch, &c->dense_tiles, &c->ovf, &c->slabs,
                     &c->gcoef, &c->feat32, &c->k32, &c->ft_cols,
                     &c->nb_seg, &c->nb_use, &c->nb_lines, &c->chk, &c->cb_scratch,
-                    &c->sc_fix, &c->sc_tab, &c->sc_acc, &c->gx_words_b, &c->gx_bits, &c->gx_prof};
+                    &c->sc_fix, &c->sc_tab, &c->sc_acc, &c->gx_words_b, &c->gx_bits, &c->gx_prof,
+                    &c->mut_out};
   for (DevBuf *b : bufs) b->release();
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
   if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
@@ -2780,6 +2785,100 @@ int kmg_gkm_scorer_score(kmg_ctx *c, const kmg_scorer *s, const uint8_t *codes, 
   KMG_TRY(gkm_scorer_score_device(c, s, c->h_codes.as<uint8_t>(), c->h_lens.as<int32_t>(), nq, ldc,
                                   maxlen, d_w, ldw, bias, c->h_out.as<double>()));
   KMG_HIP(hipMemcpyAsync(out, c->h_out.p, sizeof(double) * nq, hipMemcpyDeviceToHost, c->stream));
+  KMG_HIP(hipStreamSynchronize(c->stream));
+  return KMG_OK;
+}
+
+// ---- the substitution map (kmg_score.hip (5)): raw score differences, no diagonal, no bias
+// what both forms check before anything is allocated or launched; maxlen bounds the rows
+static int gkm_scorer_mutate_check(const kmg_scorer *s, int64_t nq, int64_t ldc, int maxlen,
+                                   const uint8_t *wts, int64_t ldw, int64_t ld_out, int64_t ld_min) {
+  if (s->kind != KMG_GKM)
+    return fail(KMG_EINVAL, "gkm scorer: the scorer was made by kmg_scorer_create");
+  if (nq < 0 || ldc <= 0 || ldc > 0x7FFFFFFF - 64) return fail(KMG_EINVAL, "bad shape");
+  if (ld_out < ld_min || ld_out > 0x7FFFFFFF - 64)
+    return fail(KMG_EINVAL, "gkm mutate: ld_out = %lld is outside [%lld, 2^31 - 65]",
+                (long long)ld_out, (long long)ld_min);
+  if (wts && ldw < std::max(0, maxlen - s->k + 1))
+    return fail(KMG_EINVAL, "gkm scorer: ldw = %lld is less than the %d words of the longest row",
+                (long long)ldw, std::max(0, maxlen - s->k + 1));
+  return KMG_OK;
+}
+
+// packs nq device rows into the context's record buffer
+static int gkm_scorer_mutate_pack(kmg_ctx *c, const uint8_t *d_codes, const int32_t *d_lens,
+                                  int64_t nq, int64_t ldc, Packed *pk) {
+  const int cw = packed_cw(ldc), mw = packed_mw(ldc);
+  KMG_TRY(c->packed.ensure(sizeof(uint32_t) * (size_t)nq * (cw + mw)));
+  *pk = Packed{c->packed.as<uint32_t>(), (int64_t)(cw + mw), cw};
+  StageTimer t(c, ST_PACK);
+  KMG_HIP(launch_pack(d_codes, d_lens, nq, ldc, 0, c->packed.as<uint32_t>(), c->stream));
+  return KMG_OK;
+}
+
+int kmg_gkm_scorer_mutate_device(kmg_ctx *c, const kmg_scorer *s, const uint8_t *d_codes,
+                                 const int32_t *d_lens, int64_t nq, int64_t ldc,
+                                 const uint8_t *d_wts, int64_t ldw, double *d_out, int64_t ld_out) {
+  if (!c || !s) return fail(KMG_EINVAL, "ctx / scorer is NULL");
+  std::lock_guard<std::mutex> lk(c->mu);
+  KMG_TRY(gkm_scorer_mutate_check(s, nq, ldc, (int)ldc, d_wts, ldw, ld_out, ldc));
+  if (nq == 0) return KMG_OK;
+  if (!d_codes || !d_lens || !d_out) return fail(KMG_EINVAL, "NULL buffer");
+  KMG_HIP(hipSetDevice(c->device));
+  c->last_call_first = (int)c->ev_log.size();
+  Packed pk{};
+  KMG_TRY(gkm_scorer_mutate_pack(c, d_codes, d_lens, nq, ldc, &pk));
+  StageTimer t(c, ST_MUTATE);
+  KMG_HIP(launch_gkm_mutate(pk, d_lens, nq, ldc, s->k, ld_out, d_wts, ldw, s->U.as<double>(), d_out,
+                            c->stream));
+  return KMG_OK;
+}
+
+int kmg_gkm_scorer_mutate(kmg_ctx *c, const kmg_scorer *s, const uint8_t *codes, const int32_t *lens,
+                          int64_t nq, int64_t ldc, const uint8_t *wts, int64_t ldw, double *out,
+                          int64_t ld_out) {
+  if (!c || !s) return fail(KMG_EINVAL, "ctx / scorer is NULL");
+  std::lock_guard<std::mutex> lk(c->mu);
+  int maxlen = 0;
+  int64_t words = 0;
+  KMG_TRY(gkm_scorer_rows(codes, lens, nq, ldc, s->k, &maxlen, &words));
+  KMG_TRY(gkm_scorer_mutate_check(s, nq, ldc, maxlen, wts, ldw, ld_out, maxlen));
+  if (nq == 0 || ld_out == 0) return KMG_OK;
+  if (!out) return fail(KMG_EINVAL, "NULL buffer");
+  KMG_HIP(hipSetDevice(c->device));
+  c->last_call_first = (int)c->ev_log.size();
+  // a slab of queries: what 256 MB of output hold, one query at the least
+  const size_t per_q = sizeof(double) * 4 * (size_t)ld_out;
+  int64_t slab = c->tune.mutate_slab > 0 ? c->tune.mutate_slab
+                                         : std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / per_q));
+  slab = std::min(slab, nq);
+  KMG_TRY(c->h_codes.ensure((size_t)nq * ldc));
+  KMG_TRY(c->h_lens.ensure(sizeof(int32_t) * (size_t)nq));
+  KMG_TRY(c->mut_out.ensure((size_t)slab * per_q));
+  KMG_HIP(hipMemcpyAsync(c->h_codes.p, codes, (size_t)nq * ldc, hipMemcpyHostToDevice, c->stream));
+  KMG_HIP(hipMemcpyAsync(c->h_lens.p, lens, sizeof(int32_t) * nq, hipMemcpyHostToDevice, c->stream));
+  const uint8_t *d_w = nullptr;
+  if (wts) {
+    KMG_TRY(c->gx_wts_in.ensure(std::max<size_t>((size_t)nq * ldw, 16)));
+    if (nq * ldw > 0)
+      KMG_HIP(hipMemcpyAsync(c->gx_wts_in.p, wts, (size_t)nq * ldw, hipMemcpyHostToDevice, c->stream));
+    d_w = c->gx_wts_in.as<uint8_t>();
+  }
+  Packed pk{};
+  KMG_TRY(gkm_scorer_mutate_pack(c, c->h_codes.as<uint8_t>(), c->h_lens.as<int32_t>(), nq, ldc, &pk));
+  for (int64_t q0 = 0; q0 < nq; q0 += slab) {
+    const int64_t nb = std::min(slab, nq - q0);
+    const Packed ps{pk.w + q0 * pk.ldp, pk.ldp, pk.cw};
+    {
+      StageTimer t(c, ST_MUTATE);
+      KMG_HIP(launch_gkm_mutate(ps, c->h_lens.as<int32_t>() + q0, nb, ldc, s->k, ld_out,
+                                d_w ? d_w + q0 * ldw : nullptr, ldw, s->U.as<double>(),
+                                c->mut_out.as<double>(), c->stream));
+    }
+    // (stream order keeps the next slab's kernel behind this copy)
+    KMG_HIP(hipMemcpyAsync(out + (size_t)q0 * 4 * ld_out, c->mut_out.p, (size_t)nb * per_q,
+                           hipMemcpyDeviceToHost, c->stream));
+  }
   KMG_HIP(hipStreamSynchronize(c->stream));
   return KMG_OK;
 }

@@ -396,6 +396,15 @@ int gkm_score_lanes(int P);
 hipError_t launch_gkm_score(const Packed &pk, int mw, int64_t nq, int l, int P, int G,
                             const uint8_t *wts, int64_t ldw, const double *U, const double *dsq,
                             double bias, double *out, hipStream_t s);
+// positions an item of the substitution map takes (8, 16, 32 or 64), from ldc alone
+int gkm_mutate_block(int64_t ldc);
+// out[q][i][b] (double [nq][ld_out][4], every element written) = S_b(i) - R(i): the sum of
+// wts[q][a] U[word a with letter b at position i] over the words a that cover i and hold no
+// other non-ACGT letter, in ascending a, minus the same sum at the query's own letter (+0.0
+// where that is not A/C/G/T); +0.0 at i >= lens[q].  ld_out >= every lens[q]
+hipError_t launch_gkm_mutate(const Packed &pk, const int32_t *lens, int64_t nq, int64_t ldc, int l,
+                             int64_t ld_out, const uint8_t *wts, int64_t ldw, const double *U,
+                             double *out, hipStream_t s);
 
 struct SeqSpec {
   const uint8_t *codes;

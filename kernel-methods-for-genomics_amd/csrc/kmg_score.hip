@@ -19,7 +19,9 @@
 //
 // Section (4) at the end is the gapped k-mer model's table scorer (kmg_gkm_scorer_*): its own
 // weight-table kernel, split by words, with 128-bit integer atomics, and its own scoring
-// kernels, several queries a wave; the butterfly (2) is shared.
+// kernels, several queries a wave; the butterfly (2) is shared.  Section (5) is that model's
+// substitution map (kmg_gkm_scorer_mutate*): the score difference of every single-letter
+// substitution of a query, one lane a (position, letter), from the same table.
 #include "kmg_internal.h"
 
 namespace kmg {
@@ -569,6 +571,125 @@ hipError_t launch_gkm_score(const Packed &pk, int mw, int64_t nq, int l, int P, 
     case 256: hipLaunchKernelGGL(gkm_score_wide_kernel, grid, dim3(256), 0, s, pk, mw, nq, l, P, wts, ldw, U, dsq, bias, out); break;
     default: return hipErrorInvalidValue;
   }
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ (5) gkm substitution map
+// kmg_gkm_scorer_mutate*: out[q][i][b] = S_b(i) - R(i), the raw score of q with letter b at
+// position i minus the raw score of q (deltaSVM's sum of l-mer weight differences):
+//   S_b(i) = sum over the words a that cover i, max(0, i - l + 1) <= a <= min(i, P - 1), whose
+//            other letters are all A/C/G/T, in ascending a from +0.0, of u[a] * U[word a with
+//            its letter at offset i - a replaced by b] (the product rounded before the add)
+//   R(i)   = S_{q_i}(i) where q_i is A/C/G/T, +0.0 where it is not
+// The order of the adds is the definition's, so no bit depends on the launch geometry.
+// One lane a (position, letter), four lanes a position; an item is S consecutive positions of
+// one query (S = 8, 16, 32, 64 from ldc alone), 64 / S items a workgroup of 256 lanes; a row
+// of any length is a run of items.  Phase 1: an item's lanes write its S + l - 1 words to LDS,
+// 8 bytes a word: the 2l-bit code; the mask of its non-ACGT letters (bit o = the letter at
+// offset o) in bits 0..11, bit 15 for a word that starts before the row or ends after it, the
+// weight byte in bits 16..23; and the S letters of its positions (4 = not A/C/G/T or past the
+// end).  Phase 2: lane (i, b) reads the l words a = i - l + 1 + j, j = 0..l - 1 (the four
+// lanes of a position the same 8 bytes, neighbouring positions neighbouring words), clears the
+// two code bits 2j, 2j + 1 of position i and sets b, issues its up to 12 table loads, then
+// adds them in ascending j.  R(i) is the sum of the lane of the quad whose b is q_i, fetched
+// by a lane permute.  No cross-lane sum; an item's results leave in one store of 32 S bytes.
+constexpr int GKM_MUT_LMAX = 12;
+
+int gkm_mutate_block(int64_t ldc) { return ldc <= 8 ? 8 : ldc <= 16 ? 16 : ldc <= 32 ? 32 : 64; }
+
+// L = l (the phase-2 loop is unrolled over it, its table values in registers); W: weighted;
+// items < 2^31 (the host checks)
+template <int L, bool W>
+__global__ __launch_bounds__(256) void gkm_mutate_kernel(Packed pk, const int32_t *__restrict__ lens,
+                                                         uint32_t items, int ldc, int ssh, int npos,
+                                                         const uint8_t *__restrict__ wts,
+                                                         int64_t ldw, const double *__restrict__ U,
+                                                         double *__restrict__ out) {
+  extern __shared__ __align__(8) uint2 mut_words[];  // [64 / S][S + l - 1], then [64 / S][S] letters
+  constexpr int l = L;
+  const int S = 1 << ssh, nw = S + l - 1, lanes = 4 * S;
+  uint8_t *slet = (uint8_t *)(mut_words + (64 >> ssh) * nw);
+  const int iw = threadIdx.x >> (ssh + 2), t = threadIdx.x & (lanes - 1);
+  const uint32_t items_row = (uint32_t)(npos + S - 1) >> ssh;
+  const uint32_t it = blockIdx.x * (64u >> ssh) + iw;
+  const bool live = it < items;
+  const int64_t q = live ? it / items_row : 0;
+  const int p0 = live ? (int)(it % items_row) << ssh : 0;
+  const int len = live ? min(max(lens[q], 0), ldc) : 0;
+  if (live) {
+    const uint32_t *rec = pk.w + q * pk.ldp;
+    for (int w = t; w < nw; w += lanes) {
+      const int a = p0 - l + 1 + w;
+      uint2 e = make_uint2(0u, 0x8000u);
+      if (a >= 0 && a + l <= len) {  // (so no read leaves the record)
+        const uint64_t v = ((uint64_t)rec[a >> 4] << 32) | rec[(a >> 4) + 1];
+        e.x = (uint32_t)((v << (2 * (a & 15))) >> (64 - 2 * l));
+        const int j = pk.cw + (a >> 5);
+        const uint64_t m = ((((uint64_t)rec[j + 1]) << 32) | rec[j]) >> (a & 31);
+        e.y = (uint32_t)(m & ((1u << l) - 1u));
+        if (W) e.y |= (uint32_t)wts[q * ldw + a] << 16;
+      }
+      mut_words[iw * nw + w] = e;
+    }
+    if (t < S) {
+      const int i = p0 + t;
+      uint32_t c = 4;
+      if (i < len && ((rec[pk.cw + (i >> 5)] >> (i & 31)) & 1u) == 0)
+        c = (rec[i >> 4] >> (30 - 2 * (i & 15))) & 3u;
+      slet[iw * S + t] = (uint8_t)c;
+    }
+  }
+  __syncthreads();
+  const int pi = t >> 2;
+  const uint32_t b = t & 3;
+  const uint2 *wd = mut_words + iw * nw + pi;
+  // every lane loads (a word that does not count reads a table entry all the same: the index
+  // is cut to the table, whatever its code bits hold); the adds alone are predicated
+  constexpr uint32_t zmask = (1u << (2 * l)) - 1u;
+  double v[L];
+  uint32_t ok = 0;
+#pragma unroll
+  for (int j = 0; j < L; ++j) {
+    const uint2 e = wd[j];  // word a = p0 + pi - (l - 1) + j: position i at its offset l - 1 - j
+    bool good = live && ((e.y & 0xFFFFu) & ~(1u << (l - 1 - j))) == 0;
+    if (W) good = good && (e.y >> 16) != 0;
+    const uint32_t z = ((e.x & ~(3u << (2 * j))) | (b << (2 * j))) & zmask;
+    v[j] = W ? (double)((e.y >> 16) & 0xFFu) * U[z] : U[z];
+    ok |= good ? 1u << j : 0u;
+  }
+  double s = 0.0;
+#pragma unroll
+  for (int j = 0; j < L; ++j) s = ((ok >> j) & 1u) ? s + v[j] : s;
+  const uint32_t qi = live ? slet[iw * S + pi] : 4u;
+  const double r = __shfl(s, (int)(qi & 3u), 4);
+  const int i = p0 + pi;
+  if (live && i < npos) out[(q * npos + i) * 4 + b] = i < len ? s - (qi < 4 ? r : 0.0) : 0.0;
+}
+
+hipError_t launch_gkm_mutate(const Packed &pk, const int32_t *lens, int64_t nq, int64_t ldc, int l,
+                             int64_t ld_out, const uint8_t *wts, int64_t ldw, const double *U,
+                             double *out, hipStream_t s) {
+  if (nq == 0 || ld_out == 0) return hipSuccess;
+  if (l < 1 || l > GKM_MUT_LMAX || ld_out > 0x7FFFFFFF - 64) return hipErrorInvalidValue;
+  const int S = gkm_mutate_block(ldc), ssh = __builtin_ctz(S), iw = 64 / S;
+  const int64_t items = nq * ((ld_out + S - 1) / S);
+  if (items > 0x7FFFFFFF) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((items + iw - 1) / iw));
+  const size_t lds = (size_t)iw * ((size_t)(S + l - 1) * sizeof(uint2) + S);
+#define KMG_MUT_CASE(LL)                                                                           \
+  case LL:                                                                                         \
+    if (wts)                                                                                       \
+      hipLaunchKernelGGL((gkm_mutate_kernel<LL, true>), grid, dim3(256), lds, s, pk, lens,         \
+                         (uint32_t)items, (int)ldc, ssh, (int)ld_out, wts, ldw, U, out);           \
+    else                                                                                           \
+      hipLaunchKernelGGL((gkm_mutate_kernel<LL, false>), grid, dim3(256), lds, s, pk, lens,        \
+                         (uint32_t)items, (int)ldc, ssh, (int)ld_out, wts, ldw, U, out);           \
+    break;
+  switch (l) {
+    KMG_MUT_CASE(1) KMG_MUT_CASE(2) KMG_MUT_CASE(3) KMG_MUT_CASE(4) KMG_MUT_CASE(5) KMG_MUT_CASE(6)
+    KMG_MUT_CASE(7) KMG_MUT_CASE(8) KMG_MUT_CASE(9) KMG_MUT_CASE(10) KMG_MUT_CASE(11) KMG_MUT_CASE(12)
+  }
+#undef KMG_MUT_CASE
   return hipGetLastError();
 }
 

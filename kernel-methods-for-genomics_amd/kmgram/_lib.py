@@ -42,7 +42,7 @@ EXPORTS = (
     "kmg_gkm_cross", "kmg_gkm_cross_device", "kmg_gkm_cross_w", "kmg_gkm_cross_w_device",
     "kmg_gkm_profile", "kmg_gkm_profile_device", "kmg_gkm_cross_f", "kmg_gkm_cross_f_device",
     "kmg_gkm_scorer_create", "kmg_gkm_scorer_score", "kmg_gkm_scorer_score_device",
-    "kmg_gkm_scorer_table",
+    "kmg_gkm_scorer_table", "kmg_gkm_scorer_mutate", "kmg_gkm_scorer_mutate_device",
 )
 KMG_FEATURES_BCAST = 1
 KMG_FACTOR_CHOLESKY, KMG_FACTOR_LU_ASYMMETRIC, KMG_FACTOR_LU_INDEFINITE = 1, 2, 3
@@ -132,6 +132,8 @@ def load():
             "kmg_gkm_scorer_score": ([P, P, P, P, I64, I64, P, I64, D, P], ctypes.c_int),
             "kmg_gkm_scorer_score_device": ([P, P, P, P, I64, I64, P, I64, D, P], ctypes.c_int),
             "kmg_gkm_scorer_table": ([P, P, P], ctypes.c_int),
+            "kmg_gkm_scorer_mutate": ([P, P, P, P, I64, I64, P, I64, P, I64], ctypes.c_int),
+            "kmg_gkm_scorer_mutate_device": ([P, P, P, P, I64, I64, P, I64, P, I64], ctypes.c_int),
             "kmg_normalize": ([P, P, I64, I64, ctypes.POINTER(I32)], ctypes.c_int),
             "kmg_center": ([P, P, I64, P, I64, I64], ctypes.c_int),
             "kmg_dmalloc": ([P, ctypes.POINTER(P), SZ], ctypes.c_int),
@@ -268,6 +270,27 @@ class GkmScorer(Scorer):
         out = np.empty(4 ** self.l, dtype=np.float64)
         check(self.ctx.lib.kmg_gkm_scorer_table(self.ctx.handle, self._h, ptr(out)))
         return out
+
+    def mutate(self, codes, lens, weights=None):
+        """float64 [nq, longest row, 4]: out[q, i, b] = f_raw(q with letter b at position i) -
+        f_raw(q), deltaSVM's sum of l-mer weight differences over the words that cover i
+        (kmg_gkm_scorer_mutate).  No bias, and no 1 / sqrt(K_qq) of a normalised model: a
+        mutant has its own diagonal.  Zero at the query's own letter and past a row's end."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        nq, ldc = codes.shape
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint8).reshape(nq, -1)
+        out = np.empty((nq, int(lens.max()) if nq else 0, 4), dtype=np.float64)
+        check(self.ctx.lib.kmg_gkm_scorer_mutate(
+            self.ctx.handle, self._h, ptr(codes), ptr(lens), nq, ldc, ptr(w),
+            0 if w is None else w.shape[1], ptr(out), out.shape[1]))
+        return out
+
+    def mutate_device(self, d_codes, d_lens, nq, ldc, d_out, ld_out, d_wts=None, ldw=0):
+        """The same on device pointers (d_out float64 [nq, ld_out, 4], ld_out >= ldc), on the
+        context stream, without synchronising."""
+        check(self.ctx.lib.kmg_gkm_scorer_mutate_device(self.ctx.handle, self._h, d_codes, d_lens,
+                                                        nq, ldc, d_wts, ldw, d_out, ld_out))
 
 
 class Context:

@@ -437,8 +437,9 @@ class EngineScorer:
 
 
 class EngineGkmScorer:
-    """What ``GramEngine.gkm_scorer`` returns: ``score(seqs, bias, weights)`` on strings and
-    ``lmer_weights()``, the 4^l l-mer weights of the model."""
+    """What ``GramEngine.gkm_scorer`` returns: ``score(seqs, bias, weights)`` on strings,
+    ``mutation_map(seqs, weights)``, the score difference of every single-letter substitution,
+    and ``lmer_weights()``, the 4^l l-mer weights of the model."""
 
     def __init__(self, engine, scorer, l, center_weights=None):
         self.engine, self._s, self.l, self._center = engine, scorer, l, center_weights
@@ -454,6 +455,25 @@ class EngineGkmScorer:
         w = GramEngine._gkm_weights("q", weights, seqs, self.l, False)
         codes, lens = E.encode(seqs)
         return self._s.score(codes, lens, bias, w)
+
+    def mutation_map(self, seqs, weights=None):
+        """float64 [len(seqs), longest row, 4]: the effect of every single-letter substitution
+        on the raw score (saturation mutagenesis; deltaSVM for every variant of a query):
+        out[q, i, b] = f_raw(seqs[q] with letter "ACGT"[b] at position i) - f_raw(seqs[q]), a sum
+        of l-mer weight differences over the at most l words that cover i, in one kernel on the
+        device (kmg_gkm_scorer_mutate).  The bias cancels; a normalised model's coef_t / sqrt(K_tt)
+        is in the table, the query's own 1 / sqrt(K_qq) is not applied (a mutant has its own
+        diagonal).  Zero at the query's own letter, past a row's end and in a row shorter than
+        l; at an N all four entries are the full sums; a word with a second non-ACGT letter
+        adds nothing.  weights and the stored center_weights as in ``score``."""
+        seqs = E.as_sequence_list(seqs)
+        if not seqs:
+            return np.zeros((0, 0, 4), dtype=np.float64)
+        if weights is None and self._center is not None:
+            weights = [P.gkm_center_weights(len(s), self.l, *self._center) for s in seqs]
+        w = GramEngine._gkm_weights("q", weights, seqs, self.l, False)
+        codes, lens = E.encode(seqs)
+        return self._s.mutate(codes, lens, w)
 
     def lmer_weights(self):
         """float64 [4^l]: the score of every l-mer under the model (deltaSVM's input), word z
